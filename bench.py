@@ -9,7 +9,14 @@ reported value is the WHOLE-JOB aggregate output tok/s.
 
 A "step" = one continuous-batching decode iteration over the full running
 batch. Synthetic random prompts, random-init bf16 weights (no network).
-TTFT p50 is measured on the prefill wave and reported alongside.
+TTFT p50 falls out of the prefill wave every run needs (timestamps only, no
+extra GPU work) and is reported alongside.
+
+A plain run does only what the headline figure needs: set up, prefill, warm
+up, time `--steps` steps, print one JSON line. `--dump-outputs DIR` also
+writes what the last timed step returned to its caller (see _dump_outputs).
+`--full` is where any further measurement or check belongs; today the
+benchmark has none, so it runs the same path.
 """
 
 import argparse
@@ -18,14 +25,65 @@ import os
 import statistics
 import time
 
-# hipBLASLt GEMM algo selection via TunableOp: load the committed gfx950
-# tuning table (profiles/tunableop_gfx950<ordinal>.csv) when present.
 _TUNE_BASE = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                           "profiles", "tunableop_gfx950.csv")
-if os.path.exists(_TUNE_BASE.replace(".csv", "0.csv")):
-    os.environ.setdefault("PYTORCH_TUNABLEOP_ENABLED", "1")
-    os.environ.setdefault("PYTORCH_TUNABLEOP_TUNING", "0")
-    os.environ.setdefault("PYTORCH_TUNABLEOP_FILENAME", _TUNE_BASE)
+
+
+def _use_tunableop_table():
+    """hipBLASLt GEMM algo selection via TunableOp: load the committed
+    gfx950 tuning table (profiles/tunableop_gfx950<ordinal>.csv) when
+    present. Must run before torch is imported."""
+    if os.path.exists(_TUNE_BASE.replace(".csv", "0.csv")):
+        os.environ.setdefault("PYTORCH_TUNABLEOP_ENABLED", "1")
+        os.environ.setdefault("PYTORCH_TUNABLEOP_TUNING", "0")
+        os.environ.setdefault("PYTORCH_TUNABLEOP_FILENAME", _TUNE_BASE)
+
+
+# --dump-outputs budget: all arrays of one rank together stay below this
+_DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def _dump_outputs(dirpath, rank, request_ids, last_outs):
+    """Write what the last timed engine.step() handed its caller.
+
+    One row per request, in submission order (request i is row i):
+      new_token_ids.npy    [n_req, window]  tokens decoded in the last step
+      output_token_ids.npy [n_req, total]   every token decoded so far (the
+                                            RequestOutput.output_token_ids)
+    float32 (token ids < 2**24 are exact), padded with -1 where a request
+    has fewer tokens or was not part of the last step's batch. Above the
+    64 MB budget a fixed seeded sample of rows is kept and its indices are
+    written as rows.npy. Ranks other than 0 add a _rank<r> suffix.
+    """
+    import numpy as np
+
+    by_id = {o.request_id: o for o in last_outs}
+
+    def table(attr):
+        cols = [list(getattr(by_id[r], attr)) if r in by_id else []
+                for r in request_ids]
+        width = max((len(c) for c in cols), default=0)
+        arr = np.full((len(cols), width), -1.0, dtype=np.float32)
+        for i, c in enumerate(cols):
+            arr[i, :len(c)] = c
+        return arr
+
+    arrays = {
+        "new_token_ids": table("new_token_ids"),
+        "output_token_ids": table("output_token_ids"),
+    }
+    row_bytes = sum(a.shape[1] * a.itemsize for a in arrays.values())
+    n = len(request_ids)
+    # rows.npy (float32 indices) is part of the budget when it is written
+    keep = _DUMP_BUDGET_BYTES // max(row_bytes + 4, 1)
+    if keep < n:
+        rows = np.sort(np.random.RandomState(0).permutation(n)[:keep])
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float32)
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), arr)
 
 
 def main():
@@ -57,8 +115,17 @@ def main():
                              "config; bf16 compute is unchanged)")
     parser.add_argument("--profile-cpu", action="store_true",
                         help="cProfile the timed loop and print hot functions")
+    parser.add_argument("--dump-outputs", dest="dump_outputs", type=str,
+                        default=None, metavar="DIR",
+                        help="after the timed steps, write the last step's "
+                             "outputs as DIR/<name>.npy (float32)")
+    parser.add_argument("--full", action="store_true",
+                        help="also run every measurement and check beyond "
+                             "the headline figure (none today: the plain "
+                             "run is already only the headline path)")
     args = parser.parse_args()
 
+    _use_tunableop_table()
     import torch
 
     from kserve_amd.engine.config import (
@@ -118,17 +185,21 @@ def main():
     engine = LLMEngine(cfg)
 
     gen = torch.Generator().manual_seed(42 + state.dp_rank)
-    sp = SamplingParams(
-        temperature=args.temperature,
-        max_tokens=max_model_len,  # never finishes inside the run
-        ignore_eos=True,
-    )
+    request_ids = [f"bench-{rank}-{i}" for i in range(args.concurrency)]
     t_submit = time.perf_counter()
-    for i in range(args.concurrency):
+    for i, request_id in enumerate(request_ids):
         prompt = torch.randint(
             0, mcfg.vocab_size, (args.prompt_len,), generator=gen
         ).tolist()
-        engine.add_request(prompt, sp, request_id=f"bench-{rank}-{i}")
+        sp = SamplingParams(
+            temperature=args.temperature,
+            max_tokens=max_model_len,  # never finishes inside the run
+            ignore_eos=True,
+            # fixed per-request seed: sampled (--temperature > 0) runs see
+            # the same random stream from process to process
+            seed=state.dp_rank * args.concurrency + i,
+        )
+        engine.add_request(prompt, sp, request_id=request_id)
 
     # ---- prefill wave (also measures TTFT) ----
     ttfts = []
@@ -151,6 +222,7 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     tokens = 0
+    outs = []
     prof = None
     if args.profile_cpu:
         import cProfile
@@ -181,6 +253,9 @@ def main():
         elapsed = float(te[0])
         tokens = int(tk[0])
 
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, rank, request_ids, outs)
+
     if prof is not None and rank == 0:
         import pstats
         import sys
@@ -198,7 +273,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1000, 3),
+            "ms_per_step": round(elapsed / max(args.steps, 1) * 1000, 3),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

@@ -13,6 +13,23 @@
 
 #define NEG_INF (-1e30f)
 
+// o_acc *= rescale must not be packed. The compiler paired these multiplies
+// into v_pk_mul_f32 with the halves of src1 swapped (op_sel:[0,1]
+// op_sel_hi:[1,0]), and on MI355X the causal v2 kernel then returned wrong,
+// call-to-call different values once the grid filled the GPU (32 x 512
+// tokens: ~0.25% of outputs, up to 0.5 off fp32; small grids were exact).
+// Rewriting exactly those 28 instructions in the emitted assembly as the
+// equivalent src0-swapped form (op_sel:[1,0] op_sel_hi:[0,1]) made the
+// kernel exact and repeatable; padding them with s_nop did not, so it is
+// the instruction form, not a neighbour hazard. Why the hardware misbehaves
+// on that form is not known. tests/test_kernel_asm.py rejects the form in
+// every kernel; tests/test_gpu_ops.py checks repeatability at that shape.
+__device__ __forceinline__ float mul_f32_unpacked(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
 namespace {
 
 constexpr int KT = 32;        // kv tokens per tile
@@ -402,7 +419,8 @@ __global__ __launch_bounds__(256) void flash_prefill_v2_kernel(
 #pragma unroll
       for (int c = 0; c < D / 16; ++c) {
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) o_acc[rt][c][reg] *= rescale[reg];
+        for (int reg = 0; reg < 4; ++reg)
+          o_acc[rt][c][reg] = mul_f32_unpacked(o_acc[rt][c][reg], rescale[reg]);
       }
 #pragma unroll
       for (int n = 0; n < KT2 / 16; ++n) {
@@ -646,7 +664,8 @@ __global__ __launch_bounds__(256) void context_prefill_kernel(
 #pragma unroll
       for (int c = 0; c < D / 16; ++c) {
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) o_acc[rt][c][reg] *= rescale[reg];
+        for (int reg = 0; reg < 4; ++reg)
+          o_acc[rt][c][reg] = mul_f32_unpacked(o_acc[rt][c][reg], rescale[reg]);
       }
 #pragma unroll
       for (int n = 0; n < KT2 / 16; ++n) {

@@ -125,3 +125,19 @@ class TestSamplerAsm:
         spills would crater the 4-pass vocab scan)."""
         asm = compile_to_asm(tmp_path, "sampling")
         assert "scratch_store" not in asm, "sampler spilled to scratch"
+
+
+class TestPackedF32Form:
+    @pytest.mark.parametrize("name", ["attention_prefill", "attention_decode"])
+    def test_no_packed_f32_with_src1_halves_swapped(self, tmp_path, name):
+        """v_pk_*_f32 with op_sel:[0,1] op_sel_hi:[1,0] (src1 halves
+        swapped) gave wrong, non-repeatable o_acc rescales in the v2
+        prefill kernel on MI355X; the kernels keep those multiplies
+        unpacked (mul_f32_unpacked). No attention kernel may contain the
+        form."""
+        asm = compile_to_asm(tmp_path, name)
+        bad = re.findall(
+            r"v_pk_\w+_f32 .*op_sel:\[0,1(?:,\d)?\] op_sel_hi:\[1,0(?:,\d)?\]",
+            asm,
+        )
+        assert not bad, f"{len(bad)} packed f32 ops with swapped src1: {bad[:3]}"
