@@ -53,10 +53,19 @@ class ModelConfig:
     # all three attention kernels (decode/flash/paged-context) as an
     # absolute-position bound since round 2.
     sliding_window: int = None
+    # weight-only quantization of the attention/MLP projections: None
+    # (bf16) or "fp8" (OCP E4M3 codes + per-channel f32 scales, W8A16;
+    # kserve_amd/ops/quant.py). lm_head and the embedding stay bf16.
+    quantization: Optional[str] = None
 
     def __post_init__(self):
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_heads
+        if self.quantization not in (None, "fp8"):
+            raise ValueError(
+                f"unknown quantization {self.quantization!r}; "
+                "supported: None, 'fp8'"
+            )
 
     @property
     def kv_bytes_per_token_per_layer(self) -> int:
@@ -142,7 +151,12 @@ class ModelConfig:
         """Parse a HuggingFace config.json (model dir contract /mnt/models)."""
         with open(config_path) as f:
             cfg = json.load(f)
+        # pre-quantized checkpoint (weight-only fp8 is how it is served:
+        # any activation scales it carries are ignored)
+        qcfg = cfg.get("quantization_config") or {}
+        quantization = "fp8" if qcfg.get("quant_method") == "fp8" else None
         return cls(
+            quantization=quantization,
             vocab_size=cfg["vocab_size"],
             hidden_size=cfg["hidden_size"],
             intermediate_size=cfg["intermediate_size"],

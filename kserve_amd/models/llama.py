@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from kserve_amd import ops
 from kserve_amd.engine.config import ModelConfig
+from kserve_amd.ops import quant
 from kserve_amd.ops.torch_ref import make_cos_sin_cache
 from kserve_amd.parallel import comm
 from kserve_amd.parallel.layers import (
@@ -65,12 +66,14 @@ class LlamaAttention(nn.Module):
             config.num_kv_heads,
             bias=config.attention_bias,
             dtype=dtype,
+            quantization=config.quantization,
         )
         self.o_proj = RowParallelLinear(
             config.num_heads * config.head_dim,
             config.hidden_size,
             bias=False,
             dtype=dtype,
+            quantization=config.quantization,
         )
         self.num_heads_local = self.qkv_proj.heads_local
         self.num_kv_heads_local = self.qkv_proj.kv_heads_local
@@ -134,9 +137,11 @@ class LlamaMLP(nn.Module):
             config.intermediate_size,
             bias=config.mlp_bias,
             dtype=dtype,
+            quantization=config.quantization,
         )
         self.down_proj = RowParallelLinear(
-            config.intermediate_size, config.hidden_size, bias=False, dtype=dtype
+            config.intermediate_size, config.hidden_size, bias=False,
+            dtype=dtype, quantization=config.quantization,
         )
 
     def forward(self, x: torch.Tensor, meta=None) -> torch.Tensor:
@@ -349,6 +354,15 @@ class LlamaForCausalLM(nn.Module):
     ):
         super().__init__()
         self.config = config
+        if config.quantization is not None and config.num_local_experts > 0:
+            # the experts are stacked bmm weights and would need a grouped
+            # fp8 kernel; quantizing only the attention projections (~5 %
+            # of the bytes) silently would be worse than refusing
+            raise ValueError(
+                f"quantization={config.quantization!r} does not support "
+                "mixture-of-experts models (num_local_experts > 0): the "
+                "stacked expert weights have no fp8 kernel"
+            )
         dtype = dtype or (
             torch.bfloat16 if config.dtype == "bfloat16" else torch.float32
         )
@@ -412,13 +426,22 @@ class LlamaForCausalLM(nn.Module):
         dev = next(self.parameters()).device
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed + comm.get_state().tp_rank)
+        # parameters() order is kept so the default (bf16) stream of
+        # random numbers is unchanged; a quantized layer draws a bf16
+        # temporary in place of its weight and quantizes it
+        quantized = {}
+        for mod in self.modules():
+            if getattr(mod, "quantization", None) is not None:
+                quantized[id(mod.qweight)] = mod
+                quantized[id(mod.weight_scale)] = None
         for p in self.parameters():
-            if p.dim() >= 2:
+            if id(p) in quantized:
+                if quantized[id(p)] is not None:
+                    quantized[id(p)].random_init_weight(std, gen)
+            elif p.dim() >= 2:
                 p.normal_(0.0, std, generator=gen)
             else:
                 p.fill_(1.0)
-        for buf_name in ():
-            pass
         return self
 
     # -- forward --------------------------------------------------------------
@@ -470,6 +493,29 @@ class LlamaForCausalLM(nn.Module):
             t = tensors[name]
             return t() if callable(t) else t
 
+        def get_w(prefix):
+            """(weight, per-channel scale or None) of one projection. A
+            projection is pre-quantized when its weight is float8_e4m3fn
+            with a sibling weight_scale (1 or out_features elements);
+            input_scale is ignored (the scheme is weight-only)."""
+            if (prefix + ".weight_scale_inv") in tensors:
+                raise ValueError(
+                    f"{prefix}.weight_scale_inv: block-wise fp8 scales are "
+                    "not supported (per-tensor or per-channel weight_scale "
+                    "only)"
+                )
+            w = get(prefix + ".weight")
+            if w.dtype != quant.FP8_DTYPE:
+                return w, None
+            if (prefix + ".weight_scale") not in tensors:
+                raise ValueError(
+                    f"{prefix}.weight is fp8 but {prefix}.weight_scale is "
+                    "missing"
+                )
+            return w, quant.expand_scale(
+                get(prefix + ".weight_scale"), w.shape[0]
+            )
+
         if self.embed_tokens is not None:
             self.embed_tokens.load_shard(get("model.embed_tokens.weight"))
         if self.norm is not None:
@@ -492,15 +538,14 @@ class LlamaForCausalLM(nn.Module):
                 qb = get(p + "self_attn.q_proj.bias")
                 kb = get(p + "self_attn.k_proj.bias")
                 vb = get(p + "self_attn.v_proj.bias")
+            qw, qs = get_w(p + "self_attn.q_proj")
+            kw, ks = get_w(p + "self_attn.k_proj")
+            vw, vs = get_w(p + "self_attn.v_proj")
             layer.self_attn.qkv_proj.load_shards(
-                get(p + "self_attn.q_proj.weight"),
-                get(p + "self_attn.k_proj.weight"),
-                get(p + "self_attn.v_proj.weight"),
-                qb,
-                kb,
-                vb,
+                qw, kw, vw, qb, kb, vb, q_scale=qs, k_scale=ks, v_scale=vs
             )
-            layer.self_attn.o_proj.load_shard(get(p + "self_attn.o_proj.weight"))
+            ow, o_s = get_w(p + "self_attn.o_proj")
+            layer.self_attn.o_proj.load_shard(ow, weight_scale=o_s)
             if isinstance(layer.mlp, MixtralMoE):
                 moe = layer.mlp
                 owned = range(
@@ -533,10 +578,13 @@ class LlamaForCausalLM(nn.Module):
                             le, gu[j][:inter], gu[j][inter:], dn[j]
                         )
             else:
+                gw, gs = get_w(p + "mlp.gate_proj")
+                uw, us = get_w(p + "mlp.up_proj")
                 layer.mlp.gate_up_proj.load_shards(
-                    get(p + "mlp.gate_proj.weight"), get(p + "mlp.up_proj.weight")
+                    gw, uw, gate_scale=gs, up_scale=us
                 )
-                layer.mlp.down_proj.load_shard(get(p + "mlp.down_proj.weight"))
+                dw, ds = get_w(p + "mlp.down_proj")
+                layer.mlp.down_proj.load_shard(dw, weight_scale=ds)
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters())

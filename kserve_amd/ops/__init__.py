@@ -239,6 +239,107 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
     return F.linear(x, weight, bias)
 
 
+# Largest token batch ops.linear_w8 sends to the fp8-weight skinny GEMM;
+# above it the weight is dequantized into the scratch buffer and hipBLASLt
+# runs the GEMM. The kernel's own limit is 256; 128 is the largest batch at
+# which it beat dequant + hipBLASLt on all four Llama-3-8B projection shapes
+# (A/B table: profiles/w8_gemm.md, tools/gemm_bench.py --w8).
+W8_MAX_TOKENS = 128
+
+# One bf16 dequant scratch per device, shared by every quantized layer
+# (same-stream ordering: a GEMM has consumed it before the next dequant
+# overwrites it). It holds HALF of the largest quantized weight: the
+# dequant path runs that weight in two row chunks, every smaller one in one
+# or two, so the scratch costs a quarter of the bytes the largest weight
+# saved instead of all of them.
+_W8_SCRATCH: dict = {}
+
+
+def w8_scratch_numel(out_features: int, in_features: int) -> int:
+    return -(-out_features // 2) * in_features
+
+
+def reserve_w8_scratch(device, out_features: int, in_features: int) -> None:
+    """Make the per-device dequant scratch large enough for a quantized
+    [out_features, in_features] weight. Layers call this when they
+    quantize/load a weight, so forward (and with it hipGraph capture) never
+    allocates."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    numel = w8_scratch_numel(out_features, in_features)
+    buf = _W8_SCRATCH.get(device)
+    if buf is None or buf.numel() < numel:
+        _W8_SCRATCH[device] = None  # drop the old one before growing
+        _W8_SCRATCH[device] = torch.empty(
+            numel, dtype=torch.bfloat16, device=device
+        )
+
+
+def _w8_scratch(device, out_features: int, in_features: int) -> torch.Tensor:
+    buf = _W8_SCRATCH.get(device)
+    if buf is None or buf.numel() < w8_scratch_numel(out_features, in_features):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(
+                "fp8 dequant scratch too small during graph capture; "
+                "call ops.reserve_w8_scratch when the weight is quantized"
+            )
+        reserve_w8_scratch(device, out_features, in_features)
+        buf = _W8_SCRATCH[device]
+    return buf
+
+
+def linear_w8(
+    x: torch.Tensor,
+    qweight: torch.Tensor,
+    scale: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Weight-only fp8 linear: (x @ qweight^T) * scale (+ bias).
+
+    qweight [M, K] float8_e4m3fn, scale [M] f32 (kserve_amd.ops.quant).
+    GPU: decode-sized batches run the fp8-weight MFMA skinny GEMM (weights
+    cross HBM once, as bytes); everything else (prefill, large batches, odd
+    shapes) dequantizes into the shared scratch and runs hipBLASLt.
+    """
+    if not x.is_cuda:
+        return torch_ref.linear_w8(x, qweight, scale, bias)
+    C = _native("linear_w8")
+    import torch.nn.functional as F
+
+    M, K = qweight.shape
+    if (
+        x.dim() == 2
+        and 0 < x.shape[0] <= W8_MAX_TOKENS
+        and M % 64 == 0
+        and K % 64 == 0
+        and x.dtype == torch.bfloat16
+        and x.stride(1) == 1
+        and x.stride(0) % 8 == 0
+        and x.data_ptr() % 16 == 0
+    ):
+        out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
+        C.skinny_gemm_w8(out, x, qweight, scale)
+        if bias is not None:
+            out += bias
+        return out
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"linear_w8 on GPU needs bf16 activations, got {x.dtype}")
+    buf = _w8_scratch(x.device, M, K)
+    rows = min(M, buf.numel() // K)
+    parts = []
+    for r0 in range(0, M, rows):
+        r1 = min(M, r0 + rows)
+        w = buf[: (r1 - r0) * K].view(r1 - r0, K)
+        C.dequant_fp8_rows(w, qweight[r0:r1], scale[r0:r1])
+        parts.append(
+            F.linear(x, w, None if bias is None else bias[r0:r1])
+        )
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+
+
 def layer_norm(x, weight, bias, eps: float):
     if x.is_cuda:
         out = torch.empty_like(x)

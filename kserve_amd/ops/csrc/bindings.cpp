@@ -57,6 +57,11 @@ hipError_t ks_skinny_gemm(void*, void*, const void*, const void*, int, int,
                           int, long, hipStream_t);
 hipError_t ks_gemm8(void*, const void*, const void*, int, int, int, int,
                     hipStream_t);
+int ks_skinny_gemm_w8_nsplit(int, int);
+hipError_t ks_skinny_gemm_w8(void*, void*, const void*, const void*,
+                             const void*, int, int, int, long, hipStream_t);
+hipError_t ks_dequant_fp8_rows(void*, const void*, const void*, long, int,
+                               hipStream_t);
 }
 
 namespace {
@@ -404,6 +409,58 @@ void skinny_gemm(at::Tensor& out, at::Tensor& x, at::Tensor& w) {
             "skinny_gemm");
 }
 
+#define CHECK_FP8_WEIGHT(q, scale)                                        \
+  TORCH_CHECK((q).scalar_type() == at::kFloat8_e4m3fn && (q).is_cuda() && \
+                  (q).dim() == 2 && (q).is_contiguous(),                  \
+              #q " must be a contiguous 2-D fp8_e4m3fn GPU tensor");      \
+  TORCH_CHECK((scale).scalar_type() == at::kFloat && (scale).is_cuda() && \
+                  (scale).is_contiguous() &&                              \
+                  (scale).numel() == (q).size(0),                         \
+              #scale " must be f32 [out_features] on GPU")
+
+void skinny_gemm_w8(at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
+                    at::Tensor& scale) {
+  // out [N, M] bf16 = (x [N, K] bf16 @ qweight [M, K]^T e4m3) * scale [M]
+  CHECK_BF16_CONTIG(out);
+  CHECK_FP8_WEIGHT(qweight, scale);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_cuda() &&
+                  x.dim() == 2 && x.stride(1) == 1,
+              "x must be bf16 row-dense");
+  int N = x.size(0);
+  int K = x.size(1);
+  int M = qweight.size(0);
+  TORCH_CHECK(qweight.size(1) == K && out.dim() == 2 && out.size(0) == N &&
+                  out.size(1) == M,
+              "shape mismatch");
+  TORCH_CHECK(N >= 1 && N <= 256 && M % 64 == 0 && K % 64 == 0,
+              "skinny_gemm_w8 needs 1 <= N <= 256, M % 64 == 0, K % 64 == 0");
+  at::Tensor ws;
+  void* wsp = nullptr;
+  const int nsplit = ks_skinny_gemm_w8_nsplit(M, K);
+  if (nsplit > 1) {
+    // bf16 partials (each a full-precision-accumulated K/nsplit dot)
+    ws = at::empty({(long)nsplit * N * M},
+                   at::TensorOptions().dtype(at::kBFloat16).device(x.device()));
+    wsp = ws.data_ptr();
+  }
+  check_hip(ks_skinny_gemm_w8(out.data_ptr(), wsp, x.data_ptr(),
+                              qweight.data_ptr(), scale.data_ptr(), M, K, N,
+                              (long)x.stride(0), current_stream()),
+            "skinny_gemm_w8");
+}
+
+void dequant_fp8_rows(at::Tensor& out, at::Tensor& qweight,
+                      at::Tensor& scale) {
+  // out [M, K] bf16 = bf16(float(qweight [M, K] e4m3) * scale [M])
+  CHECK_BF16_CONTIG(out);
+  CHECK_FP8_WEIGHT(qweight, scale);
+  TORCH_CHECK(out.numel() == qweight.numel(), "shape mismatch");
+  check_hip(ks_dequant_fp8_rows(out.data_ptr(), qweight.data_ptr(),
+                                scale.data_ptr(), (long)qweight.size(0),
+                                (int)qweight.size(1), current_stream()),
+            "dequant_fp8_rows");
+}
+
 void gemm8(at::Tensor& d, at::Tensor& a, at::Tensor& w, int64_t swizzle) {
   // EXPERIMENTAL (see gemm8.hip header): not used by ops.linear dispatch
   CHECK_BF16_CONTIG(d);
@@ -451,6 +508,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk_topp_sample", &topk_topp_sample,
         "fused top-k/top-p + Gumbel-max sampler (radix-histogram select)");
   m.def("skinny_gemm", &skinny_gemm, "decode GEMM (N<=256, MFMA streaming)");
+  m.def("skinny_gemm_w8", &skinny_gemm_w8,
+        "decode GEMM, fp8 e4m3 weights x bf16 activations (N<=256)");
+  m.def("dequant_fp8_rows", &dequant_fp8_rows,
+        "fp8 e4m3 rows * per-row scale -> bf16");
   m.def("gemm8", &gemm8,
         "EXPERIMENTAL 8-phase 256x256 MFMA GEMM (round-2 candidate)");
   m.def("mfma_probe", &mfma_probe, "MFMA layout probe (tests)");

@@ -310,3 +310,18 @@ def fused_add_layer_norm(
 
 def gelu(x: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.gelu(x.float()).to(x.dtype)
+
+
+def linear_w8(
+    x: torch.Tensor,
+    qweight: torch.Tensor,
+    scale: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Weight-only fp8 linear, fp32 reference: x [.., K] @ qweight [M, K]^T
+    (e4m3 codes, exact in fp32), per-channel scale applied in fp32 AFTER the
+    K reduction — the order the HIP kernel uses."""
+    y = (x.float() @ qweight.float().t()) * scale.float()[None, :]
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)

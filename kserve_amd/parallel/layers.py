@@ -16,6 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from kserve_amd import ops
+from kserve_amd.ops import quant
 from kserve_amd.parallel import comm
 
 
@@ -24,7 +25,85 @@ def _divide(a: int, b: int) -> int:
     return a // b
 
 
-class ColumnParallelLinear(nn.Module):
+class _QuantLinearBase(nn.Module):
+    """Weight storage shared by the parallel linears.
+
+    quantization=None: a ``weight`` parameter in the model dtype.
+    quantization="fp8": ``qweight`` (float8_e4m3fn) + ``weight_scale``
+    (f32 [out_local]) INSTEAD of ``weight`` — the layer never holds both
+    copies (kserve_amd.ops.quant has the format).
+    """
+
+    def _alloc_weight(
+        self, out_local: int, in_local: int, dtype: torch.dtype,
+        quantization: Optional[str],
+    ) -> None:
+        self.quantization = quant.check_quantization(quantization)
+        if self.quantization == "fp8":
+            self.qweight = nn.Parameter(
+                torch.empty(out_local, in_local, dtype=quant.FP8_DTYPE),
+                requires_grad=False,
+            )
+            self.weight_scale = nn.Parameter(
+                torch.empty(out_local, dtype=torch.float32),
+                requires_grad=False,
+            )
+        else:
+            self.weight = nn.Parameter(
+                torch.empty(out_local, in_local, dtype=dtype),
+                requires_grad=False,
+            )
+
+    def _to_fp8(self, w: torch.Tensor, scale: Optional[torch.Tensor]):
+        """One already-sliced shard -> (codes, per-channel scale) on the
+        layer's device. ``scale`` is the matching slice of a pre-quantized
+        checkpoint's per-channel scale (None for a bf16/f32 shard, which is
+        quantized here, after slicing, so scales are per rank)."""
+        dev = self.qweight.device
+        if w.dtype == quant.FP8_DTYPE:
+            if scale is None:
+                raise ValueError("fp8 checkpoint weight without weight_scale")
+            return w.to(dev), scale.float().to(dev)
+        return quant.quantize_fp8_per_channel(w.to(dev))
+
+    def _store_weight(self, pieces, scales=None) -> None:
+        """Store this rank's shard, given as row-blocks that are
+        concatenated along the output dim (fused QKV / gate+up)."""
+        scales = scales or [None] * len(pieces)
+        if self.quantization == "fp8":
+            qs = [self._to_fp8(w, s) for w, s in zip(pieces, scales)]
+            self.qweight.data.copy_(torch.cat([q for q, _ in qs], dim=0))
+            self.weight_scale.data.copy_(torch.cat([s for _, s in qs], dim=0))
+            ops.reserve_w8_scratch(self.qweight.device, *self.qweight.shape)
+            return
+        dt = self.weight.dtype
+        ws = [
+            quant.dequantize_fp8(w, s, dt) if w.dtype == quant.FP8_DTYPE
+            else w.to(dt)
+            for w, s in zip(pieces, scales)
+        ]
+        self.weight.data.copy_(torch.cat(ws, dim=0))
+
+    @torch.no_grad()
+    def random_init_weight(self, std: float, generator) -> None:
+        """normal_ does not exist for fp8: draw a temporary in bf16 on the
+        layer's device and quantize it."""
+        if self.quantization == "fp8":
+            tmp = torch.empty(
+                self.qweight.shape, dtype=torch.bfloat16,
+                device=self.qweight.device,
+            ).normal_(0.0, std, generator=generator)
+            self._store_weight([tmp])
+        else:
+            self.weight.normal_(0.0, std, generator=generator)
+
+    def _linear(self, x: torch.Tensor, bias: Optional[torch.Tensor] = None):
+        if self.quantization == "fp8":
+            return ops.linear_w8(x, self.qweight, self.weight_scale, bias)
+        return ops.linear(x, self.weight, bias)
+
+
+class ColumnParallelLinear(_QuantLinearBase):
     """Y_shard = X @ W_shard^T; output features sharded across TP ranks."""
 
     def __init__(
@@ -34,6 +113,7 @@ class ColumnParallelLinear(nn.Module):
         bias: bool = False,
         dtype: torch.dtype = torch.bfloat16,
         gather_output: bool = False,
+        quantization: Optional[str] = None,
     ):
         super().__init__()
         st = comm.get_state()
@@ -42,10 +122,7 @@ class ColumnParallelLinear(nn.Module):
         self.out_features = out_features
         self.out_per_rank = _divide(out_features, self.tp_size)
         self.gather_output = gather_output
-        self.weight = nn.Parameter(
-            torch.empty(self.out_per_rank, in_features, dtype=dtype),
-            requires_grad=False,
-        )
+        self._alloc_weight(self.out_per_rank, in_features, dtype, quantization)
         self.bias = (
             nn.Parameter(
                 torch.empty(self.out_per_rank, dtype=dtype), requires_grad=False
@@ -55,21 +132,31 @@ class ColumnParallelLinear(nn.Module):
         )
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        y = ops.linear(x, self.weight, self.bias)
+        y = self._linear(x, self.bias)
         if self.gather_output and self.tp_size > 1:
             y = comm.tp_all_gather(y, dim=-1)
         return y
 
-    def load_shard(self, full_weight: torch.Tensor, full_bias: Optional[torch.Tensor] = None):
-        """Slice the full tensor for this rank (rows = output features)."""
+    def load_shard(
+        self,
+        full_weight: torch.Tensor,
+        full_bias: Optional[torch.Tensor] = None,
+        weight_scale: Optional[torch.Tensor] = None,
+    ):
+        """Slice the full tensor for this rank (rows = output features).
+        ``weight_scale``: per-channel f32 scale of a pre-quantized (fp8)
+        ``full_weight``."""
         r = comm.get_state().tp_rank
         lo, hi = r * self.out_per_rank, (r + 1) * self.out_per_rank
-        self.weight.data.copy_(full_weight[lo:hi].to(self.weight.dtype))
+        self._store_weight(
+            [full_weight[lo:hi]],
+            [None if weight_scale is None else weight_scale[lo:hi]],
+        )
         if self.bias is not None and full_bias is not None:
             self.bias.data.copy_(full_bias[lo:hi].to(self.bias.dtype))
 
 
-class QKVParallelLinear(nn.Module):
+class QKVParallelLinear(_QuantLinearBase):
     """Fused QKV projection, head-sharded. Output layout per rank:
     [q_heads_local*D | kv_heads_local*D | kv_heads_local*D]."""
 
@@ -81,6 +168,7 @@ class QKVParallelLinear(nn.Module):
         num_kv_heads: int,
         bias: bool = False,
         dtype: torch.dtype = torch.bfloat16,
+        quantization: Optional[str] = None,
     ):
         super().__init__()
         st = comm.get_state()
@@ -99,9 +187,7 @@ class QKVParallelLinear(nn.Module):
         out_local = (self.heads_local + 2 * self.kv_heads_local) * head_dim
         self.q_size = self.heads_local * head_dim
         self.kv_size = self.kv_heads_local * head_dim
-        self.weight = nn.Parameter(
-            torch.empty(out_local, hidden_size, dtype=dtype), requires_grad=False
-        )
+        self._alloc_weight(out_local, hidden_size, dtype, quantization)
         self.bias = (
             nn.Parameter(torch.empty(out_local, dtype=dtype), requires_grad=False)
             if bias
@@ -109,7 +195,7 @@ class QKVParallelLinear(nn.Module):
         )
 
     def forward(self, x: torch.Tensor):
-        qkv = ops.linear(x, self.weight, self.bias)
+        qkv = self._linear(x, self.bias)
         return qkv.split([self.q_size, self.kv_size, self.kv_size], dim=-1)
 
     def load_shards(
@@ -120,7 +206,12 @@ class QKVParallelLinear(nn.Module):
         q_bias: Optional[torch.Tensor] = None,
         k_bias: Optional[torch.Tensor] = None,
         v_bias: Optional[torch.Tensor] = None,
+        q_scale: Optional[torch.Tensor] = None,
+        k_scale: Optional[torch.Tensor] = None,
+        v_scale: Optional[torch.Tensor] = None,
     ):
+        """``*_scale``: per-channel f32 scales of pre-quantized (fp8)
+        projections; the fused layer concatenates the sliced vectors."""
         r = comm.get_state().tp_rank
         D = self.head_dim
         q_lo = r * self.heads_local * D
@@ -128,10 +219,14 @@ class QKVParallelLinear(nn.Module):
         kv_rank = r // self.kv_replication
         kv_lo = kv_rank * self.kv_heads_local * D
         kv_hi = kv_lo + self.kv_heads_local * D
-        w = torch.cat(
-            [q_weight[q_lo:q_hi], k_weight[kv_lo:kv_hi], v_weight[kv_lo:kv_hi]], dim=0
+        self._store_weight(
+            [q_weight[q_lo:q_hi], k_weight[kv_lo:kv_hi], v_weight[kv_lo:kv_hi]],
+            [
+                None if q_scale is None else q_scale[q_lo:q_hi],
+                None if k_scale is None else k_scale[kv_lo:kv_hi],
+                None if v_scale is None else v_scale[kv_lo:kv_hi],
+            ],
         )
-        self.weight.data.copy_(w.to(self.weight.dtype))
         if self.bias is not None and q_bias is not None:
             b = torch.cat(
                 [q_bias[q_lo:q_hi], k_bias[kv_lo:kv_hi], v_bias[kv_lo:kv_hi]], dim=0
@@ -139,7 +234,7 @@ class QKVParallelLinear(nn.Module):
             self.bias.data.copy_(b.to(self.bias.dtype))
 
 
-class RowParallelLinear(nn.Module):
+class RowParallelLinear(_QuantLinearBase):
     """Y = sum_ranks(X_shard @ W_shard^T); input features sharded; output
     all-reduced (the per-layer RCCL call over xGMI).
 
@@ -163,6 +258,7 @@ class RowParallelLinear(nn.Module):
         dtype: torch.dtype = torch.bfloat16,
         reduce_output: bool = True,
         overlap_chunks: int = 2,
+        quantization: Optional[str] = None,
     ):
         super().__init__()
         st = comm.get_state()
@@ -170,10 +266,7 @@ class RowParallelLinear(nn.Module):
         self.in_per_rank = _divide(in_features, self.tp_size)
         self.out_features = out_features
         self.reduce_output = reduce_output
-        self.weight = nn.Parameter(
-            torch.empty(out_features, self.in_per_rank, dtype=dtype),
-            requires_grad=False,
-        )
+        self._alloc_weight(out_features, self.in_per_rank, dtype, quantization)
         # bias added once (rank 0 semantics handled by adding after reduce)
         self.bias = (
             nn.Parameter(torch.empty(out_features, dtype=dtype), requires_grad=False)
@@ -198,10 +291,16 @@ class RowParallelLinear(nn.Module):
             parts = []
             works = []
             for c in range(n):
-                wc = self.weight[c * step : (c + 1) * step]
-                if wc.shape[0] == 0:
+                rows = slice(c * step, (c + 1) * step)
+                if c * step >= self.out_features:
                     break
-                yc = ops.linear(x, wc)
+                if self.quantization == "fp8":
+                    # codes and their scales are sliced together
+                    yc = ops.linear_w8(
+                        x, self.qweight[rows], self.weight_scale[rows]
+                    )
+                else:
+                    yc = ops.linear(x, self.weight[rows])
                 works.append(comm.tp_all_reduce_async(yc))
                 parts.append(yc)
             for w in works:
@@ -211,7 +310,7 @@ class RowParallelLinear(nn.Module):
             if self.bias is not None:
                 y = y + self.bias
             return y
-        y = ops.linear(x, self.weight)
+        y = self._linear(x)
         if delta is not None:
             # per-rank partial (e.g. LoRA with A column-sharded): must be
             # summed by the same all-reduce as the main GEMM
@@ -222,15 +321,24 @@ class RowParallelLinear(nn.Module):
             y = y + self.bias
         return y
 
-    def load_shard(self, full_weight: torch.Tensor, full_bias: Optional[torch.Tensor] = None):
+    def load_shard(
+        self,
+        full_weight: torch.Tensor,
+        full_bias: Optional[torch.Tensor] = None,
+        weight_scale: Optional[torch.Tensor] = None,
+    ):
+        """Slice this rank's input features, then quantize: every rank gets
+        its own per-channel scales, so its partial is correctly scaled
+        before the all-reduce. A pre-quantized checkpoint's per-channel
+        scale applies to every column slice unchanged."""
         r = comm.get_state().tp_rank
         lo, hi = r * self.in_per_rank, (r + 1) * self.in_per_rank
-        self.weight.data.copy_(full_weight[:, lo:hi].to(self.weight.dtype))
+        self._store_weight([full_weight[:, lo:hi]], [weight_scale])
         if self.bias is not None and full_bias is not None:
             self.bias.data.copy_(full_bias.to(self.bias.dtype))
 
 
-class MergedColumnParallelLinear(nn.Module):
+class MergedColumnParallelLinear(_QuantLinearBase):
     """Fused gate+up projection (SwiGLU MLP), each half column-sharded.
 
     Per-rank output layout: [gate_local | up_local] so silu_and_mul can
@@ -242,14 +350,14 @@ class MergedColumnParallelLinear(nn.Module):
         out_features_each: int,
         bias: bool = False,
         dtype: torch.dtype = torch.bfloat16,
+        quantization: Optional[str] = None,
     ):
         super().__init__()
         st = comm.get_state()
         self.tp_size = st.tp_size
         self.each_per_rank = _divide(out_features_each, self.tp_size)
-        self.weight = nn.Parameter(
-            torch.empty(2 * self.each_per_rank, in_features, dtype=dtype),
-            requires_grad=False,
+        self._alloc_weight(
+            2 * self.each_per_rank, in_features, dtype, quantization
         )
         self.bias = (
             nn.Parameter(
@@ -260,13 +368,24 @@ class MergedColumnParallelLinear(nn.Module):
         )
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return ops.linear(x, self.weight, self.bias)
+        return self._linear(x, self.bias)
 
-    def load_shards(self, gate_weight: torch.Tensor, up_weight: torch.Tensor):
+    def load_shards(
+        self,
+        gate_weight: torch.Tensor,
+        up_weight: torch.Tensor,
+        gate_scale: Optional[torch.Tensor] = None,
+        up_scale: Optional[torch.Tensor] = None,
+    ):
         r = comm.get_state().tp_rank
         lo, hi = r * self.each_per_rank, (r + 1) * self.each_per_rank
-        w = torch.cat([gate_weight[lo:hi], up_weight[lo:hi]], dim=0)
-        self.weight.data.copy_(w.to(self.weight.dtype))
+        self._store_weight(
+            [gate_weight[lo:hi], up_weight[lo:hi]],
+            [
+                None if gate_scale is None else gate_scale[lo:hi],
+                None if up_scale is None else up_scale[lo:hi],
+            ],
+        )
 
 
 class VocabParallelEmbedding(nn.Module):

@@ -50,6 +50,24 @@ def detect_backend(model_dir: str) -> str:
     return "encoder"
 
 
+def engine_model_config(args):
+    """ModelConfig for the engine backend: config.json plus the CLI flags
+    that change the model itself."""
+    from kserve_amd.engine.config import ModelConfig
+
+    model_cfg = ModelConfig.from_hf_config(
+        os.path.join(args.model_dir, "config.json")
+    )
+    if getattr(args, "expert_parallel", False):
+        model_cfg.expert_parallel = True
+    # --quantization fp8: a bf16 checkpoint is quantized at load; a
+    # pre-quantized one already set it from its quantization_config
+    quantization = getattr(args, "quantization", None)
+    if quantization not in (None, "none"):
+        model_cfg.quantization = quantization
+    return model_cfg
+
+
 def build_model(args):
     backend = getattr(args, "backend", None) or detect_backend(args.model_dir)
     logger.info("huggingfaceserver backend: %s", backend)
@@ -73,11 +91,7 @@ def build_model(args):
         from transformers import AutoTokenizer
 
         tokenizer = AutoTokenizer.from_pretrained(args.model_dir)
-        model_cfg = ModelConfig.from_hf_config(
-            os.path.join(args.model_dir, "config.json")
-        )
-        if getattr(args, "expert_parallel", False):
-            model_cfg.expert_parallel = True
+        model_cfg = engine_model_config(args)
         # draft-model speculation (vLLM --speculative-config equivalent)
         draft_cfg = None
         draft_dir = getattr(args, "speculative_draft_model", None)
@@ -141,8 +155,8 @@ def build_model(args):
     return model
 
 
-def main(argv=None):
-    from kserve_amd.model_server import ModelServer, build_arg_parser
+def build_parser():
+    from kserve_amd.model_server import build_arg_parser
 
     parser = build_arg_parser()
     parser.add_argument("--backend", default=None, choices=["engine", "encoder", "hf"])
@@ -163,6 +177,9 @@ def main(argv=None):
     parser.add_argument("--kv-offload-bytes", dest="kv_offload_bytes", type=int, default=0)
     parser.add_argument("--kv-cache-dtype", dest="kv_cache_dtype", default="auto",
                         choices=["auto", "fp8"])
+    # weight-only fp8 (E4M3) for the attention/MLP projections
+    parser.add_argument("--quantization", dest="quantization", default=None,
+                        choices=["none", "fp8"])
     # LoRA adapter serving (reference: --enable-lora --lora-modules name=path)
     parser.add_argument("--speculative-draft-model",
                         dest="speculative_draft_model", default=None,
@@ -178,7 +195,13 @@ def main(argv=None):
         "--lora-modules", dest="lora_modules", nargs="*", default=[],
         help="name=path pairs; each name becomes a served model id",
     )
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    from kserve_amd.model_server import ModelServer
+
+    args = build_parser().parse_args(argv)
     configure_logging()
     model = build_model(args)
     ModelServer(

@@ -3,6 +3,13 @@
 shape, to judge hipBLASLt (tuned/untuned) against the HBM roofline.
 
 Run on GPU: python tools/gemm_bench.py [--tune]
+            python tools/gemm_bench.py --w8 [--out FILE.md]
+
+--w8 is the A/B behind ops.W8_MAX_TOKENS (profiles/w8_gemm.md): per
+Llama-3-8B projection shape and token batch it times, in one process and
+interleaved, (a) ops.linear on bf16 weights, (b) the fp8-weight skinny GEMM
+and (c) dequant + hipBLASLt, the path ops.linear_w8 takes above the
+threshold.
 """
 
 import argparse
@@ -14,6 +21,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 parser = argparse.ArgumentParser()
 parser.add_argument("--tune", action="store_true")
 parser.add_argument("--iters", type=int, default=50)
+parser.add_argument("--w8", action="store_true",
+                    help="fp8-weight A/B table instead of the bf16 table")
+parser.add_argument("--out", default=None,
+                    help="--w8: also write the table as markdown here")
 args = parser.parse_args()
 
 if args.tune:
@@ -52,6 +63,112 @@ SHAPES = [
 ]
 
 import kserve_amd_C
+
+
+def bench_w8():
+    """One row per (shape, N): median-of-rounds us for the three variants,
+    rounds interleaved so drift hits all three alike. Each call streams a
+    different weight copy (the set is larger than the 256 MB Infinity
+    Cache), as consecutive layers do in a model; TB/s is weight bytes of
+    the variant's own format over its time."""
+    import statistics
+
+    from kserve_amd import ops
+    from kserve_amd.ops.quant import quantize_fp8_per_channel
+
+    shapes = [  # (name, K in, M out): Llama-3-8B projections
+        ("qkv", 4096, 6144),
+        ("o", 4096, 4096),
+        ("gate_up", 4096, 28672),
+        ("down", 14336, 4096),
+    ]
+    batches = [1, 16, 64, 128, 256]
+    rounds = 5
+    for _, K, M in shapes:
+        ops.reserve_w8_scratch(dev, M, K)
+
+    def timed(fn, copies, iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for i in range(iters):
+            fn(i % copies)
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / iters * 1000
+
+    lines = [
+        "| shape | K | M | N | (a) bf16 us | (a) TB/s | (b) w8 us | (b) TB/s "
+        "| (c) dequant+GEMM us | (b)/(a) | (b)<=(c) |",
+        "|---|---|---|---|---|---|---|---|---|---|---|",
+    ]
+    print(lines[0]); print(lines[1])
+    worst = {n: True for n in batches}
+    for name, K, M in shapes:
+        copies = max(2, -(-(768 << 20) // (M * K)))
+        gen = torch.Generator(device=dev).manual_seed(0)
+        ws, qs, ss = [], [], []
+        for _ in range(copies):
+            w = torch.randn(M, K, dtype=torch.bfloat16, device=dev,
+                            generator=gen) * 0.02
+            q, s = quantize_fp8_per_channel(w)
+            ws.append(w); qs.append(q); ss.append(s)
+        for N in batches:
+            x = torch.randn(N, K, dtype=torch.bfloat16, device=dev,
+                            generator=gen) / 8
+            out = torch.empty(N, M, dtype=torch.bfloat16, device=dev)
+
+            def fa(i):
+                return ops.linear(x, ws[i])
+
+            def fb(i):
+                kserve_amd_C.skinny_gemm_w8(out, x, qs[i], ss[i])
+
+            def fc(i):
+                return ops.linear_w8(x, qs[i], ss[i])
+
+            iters = max(args.iters, 2 * copies)
+            res = {"a": [], "b": [], "c": []}
+            keep = ops.W8_MAX_TOKENS
+            try:
+                for r in range(rounds + 1):  # round 0 is warm-up
+                    for key, fn in (("a", fa), ("b", fb), ("c", fc)):
+                        ops.W8_MAX_TOKENS = 0 if key == "c" else keep
+                        t = timed(fn, copies, iters)
+                        if r:
+                            res[key].append(t)
+            finally:
+                ops.W8_MAX_TOKENS = keep
+            a, b, c = (statistics.median(res[k]) for k in "abc")
+            spread = max(
+                (max(res[k]) - min(res[k])) / statistics.median(res[k])
+                for k in "abc"
+            )
+            ok = b <= c
+            worst[N] = worst[N] and ok
+            line = (
+                f"| {name} | {K} | {M} | {N} | {a:.1f} | "
+                f"{M * K * 2 / a / 1e6:.2f} | {b:.1f} | {M * K / b / 1e6:.2f} "
+                f"| {c:.1f} | {b / a:.2f} | {'yes' if ok else 'no'} |"
+            )
+            print(line + f"  spread {spread:.0%}", flush=True)
+            lines.append(line)
+        del ws, qs, ss
+        torch.cuda.empty_cache()
+    # largest N such that (b) <= (c) on all four shapes (0 if none)
+    chosen = max([n for n in batches if worst[n]], default=0)
+    tail = f"\nW8_MAX_TOKENS by this table: {chosen}"
+    print(tail)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n" + tail + "\n")
+
+
+if args.w8:
+    bench_w8()
+    sys.exit(0)
+
 
 def bench_custom(x, w, iters):
     out = torch.empty(x.shape[0], w.shape[0], dtype=torch.bfloat16, device=dev)

@@ -83,6 +83,8 @@ def main():
     ap.add_argument("--max-tokens", type=int, default=128)
     ap.add_argument("--kv-cache-dtype", default="auto",
                     choices=["auto", "fp8"])
+    ap.add_argument("--quantization", default="none",
+                    choices=["none", "fp8"])
     args = ap.parse_args()
 
     import random
@@ -106,6 +108,8 @@ def main():
         mcfg = ModelConfig.llama3_70b()
     else:
         mcfg = ModelConfig.tiny(vocab_size=1024)
+    if args.quantization != "none":
+        mcfg.quantization = args.quantization
     cfg = EngineConfig(
         model=mcfg,
         cache=CacheConfig(block_size=16,
