@@ -100,6 +100,19 @@ class ModelRunner:
     def _num_local_layers(self) -> int:
         return getattr(self.model, "num_local_layers", self.config.model.num_layers)
 
+    def _kv_allocator(self):
+        """Allocator of the KV cache pools: zero-filling on every device.
+
+        The attention kernels bound the tokens they *use* by context_lens,
+        but they load whole pages and weight the slots past it with p = 0
+        (``acc += p * v``), so a NaN or Inf in a never-written slot becomes
+        NaN in the output. Their contract is: exact for any finite stale
+        data, undefined for non-finite. The cache must therefore never hold
+        non-finite values the model did not write, which uninitialised
+        memory (torch.empty) does not promise. Zeroing the pool once at
+        startup costs seconds even at hundreds of GB."""
+        return torch.zeros
+
     def allocate_kv_cache(self, num_blocks: int):
         m = self.config.model
         kv_heads_local = max(1, m.num_kv_heads // max(1, self._tp_size()))
@@ -110,9 +123,7 @@ class ModelRunner:
             m.head_dim,
         )
         dtype = self.config.cache.cache_torch_dtype(self.model.dtype)
-        # empty, not zeros: context_lens bound all reads, and zeroing a
-        # 250 GB pool costs seconds of startup
-        alloc = torch.empty if self.is_cuda else torch.zeros
+        alloc = self._kv_allocator()
         self.kv_caches = [
             (
                 alloc(shape, dtype=dtype, device=self.device),

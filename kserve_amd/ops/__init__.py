@@ -100,6 +100,16 @@ def paged_attention_decode(
     out: Optional[torch.Tensor] = None,
     window: int = 0,
 ) -> torch.Tensor:
+    """Single-token attention of each sequence against its paged context.
+
+    block_tables [S, max_blocks] may be wider than any sequence needs; only
+    the first ceil(context_lens / block_size) entries of a row select pages,
+    the rest must still be valid block ids. Cache contract: the kernels load
+    whole pages and give slots at or past context_lens (and before the
+    window) weight 0, so the result is exact for ANY FINITE stale data in
+    those slots and undefined (NaN) for non-finite data. The cache must
+    never hold non-finite values the model did not write; the engine
+    allocates it zero-filled (ModelRunner._kv_allocator)."""
     if q.is_cuda:
         if out is None:
             out = torch.empty_like(q)
@@ -149,7 +159,13 @@ def context_attention_varlen(
     """Prefill attention against the paged cache (chunked prefill): the
     chunk's KV must already be written to the cache; queries attend causally
     to the whole per-seq context (bounded below by the sliding window when
-    window > 0)."""
+    window > 0).
+
+    Cache contract, as for paged_attention_decode: exact for any finite
+    stale data in slots at or past context_lens and in pages behind unused
+    block-table entries (which must be valid ids), undefined for non-finite
+    data there; the cache must never hold non-finite values the model did
+    not write."""
     if q.is_cuda:
         out = torch.empty_like(q)
         _native("context_prefill").context_prefill_varlen(

@@ -241,6 +241,11 @@ __global__ __launch_bounds__(256) void topk_topp_sample_kernel(
   const unsigned int thr = sh_thresh;
 
   // ---- pass D: Gumbel-argmax over the surviving set ----
+  // top_k == 1 is argmax: every logit tied with the maximum survives the
+  // threshold (the k-th VALUE is exact, its ties are kept), and Gumbel noise
+  // would pick among them at random. Without noise the ties fall to the
+  // lowest index, exactly as greedy_sample breaks them.
+  const bool argmax_only = (k == 1);
   float best = -1e38f;
   int best_idx = 0;
   for (int i = tid; i < V; i += 256) {
@@ -248,7 +253,8 @@ __global__ __launch_bounds__(256) void topk_topp_sample_kernel(
     if (bf16_sort_key(b) < thr) continue;
     const unsigned int h = hash2(seed, (unsigned int)i);
     const float u = ((float)h + 1.0f) * 2.3283064e-10f;
-    const float val = bf16_bits_to_float(b) * inv_t - __logf(-__logf(u));
+    const float val = bf16_bits_to_float(b) * inv_t -
+                      (argmax_only ? 0.f : __logf(-__logf(u)));
     if (val > best) { best = val; best_idx = i; }
   }
 #pragma unroll

@@ -370,3 +370,36 @@ class TestSampledWindows:
         # no windows: one token per step (prefill samples the first token,
         # then 5 single-token decode steps)
         assert steps >= 6
+
+
+@pytest.mark.parametrize("kv_dtype", ["auto", "fp8"])
+def test_gpu_kv_cache_allocation_is_zero_filled(engine, monkeypatch, kv_dtype):
+    """The attention kernels are exact for any finite stale cache data and
+    undefined for non-finite, so the pool the runner allocates for a GPU
+    must not be uninitialised memory. No GPU needed: flip the runner's
+    device flag, forbid torch.empty, and look at what it allocates."""
+    from kserve_amd.engine import model_runner as mr
+
+    runner = engine.runner
+    assert runner._kv_allocator() is torch.zeros
+    saved = (runner.is_cuda, runner.kv_caches, runner.num_gpu_blocks,
+             runner.config.cache.kv_cache_dtype)
+
+    def no_empty(*a, **k):
+        raise AssertionError("KV cache allocated with torch.empty")
+
+    monkeypatch.setattr(runner, "is_cuda", True)
+    monkeypatch.setattr(runner, "_allocate_cpu_kv", lambda: None)
+    monkeypatch.setattr(runner.config.cache, "kv_cache_dtype", kv_dtype)
+    monkeypatch.setattr(mr.torch, "empty", no_empty)
+    try:
+        runner.allocate_kv_cache(3)
+        assert len(runner.kv_caches) == runner._num_local_layers()
+        for k, v in runner.kv_caches:
+            assert k.shape[0] == 3
+            assert not bool(k.view(torch.uint8).any())
+            assert not bool(v.view(torch.uint8).any())
+    finally:
+        monkeypatch.undo()
+        (runner.is_cuda, runner.kv_caches, runner.num_gpu_blocks,
+         runner.config.cache.kv_cache_dtype) = saved

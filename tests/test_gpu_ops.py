@@ -463,6 +463,36 @@ class TestSampling:
         torch.cuda.synchronize()
         assert (out1 == out2).all()
 
+    def test_topk1_is_argmax_with_ties(self, dev):
+        """top_k=1 must give greedy's token for every seed, also when several
+        logits tie for the maximum in bf16 (random small models do this): the
+        lowest index wins, as in greedy_sample."""
+        import kserve_amd_C
+
+        from kserve_amd import ops
+
+        S, V = 64, 2051  # V not a multiple of 8 or 256
+        torch.manual_seed(12)
+        logits = torch.randn(S, V, dtype=torch.bfloat16, device=dev)
+        top = logits.float().max(dim=-1).values.to(torch.bfloat16)
+        # 1-4 extra copies of each row's maximum at random places
+        g = torch.Generator().manual_seed(3)
+        for s in range(S):
+            idx = torch.randint(0, V, (1 + s % 4,), generator=g)
+            logits[s, idx.to(dev)] = top[s]
+        want = ops.greedy_sample(logits)
+        ref = (logits.float() == logits.float().max(-1, keepdim=True).values)
+        assert torch.equal(want.cpu(), ref.cpu().float().argmax(-1))
+        assert int(ref.sum(-1).min()) >= 2
+        temps = torch.full((S,), 0.7, dtype=torch.float32, device=dev)
+        top_p = torch.ones(S, dtype=torch.float32, device=dev)
+        top_k = torch.ones(S, dtype=torch.int32, device=dev)
+        for base in (0, 5, 1 << 20):
+            seeds = torch.arange(S, dtype=torch.int64, device=dev) * 7919 + base
+            out = torch.empty(S, dtype=torch.int64, device=dev)
+            kserve_amd_C.topk_topp_sample(out, logits, temps, top_p, top_k, seeds)
+            assert torch.equal(out, want)
+
 
 class TestSkinnyGemm:
     @pytest.mark.parametrize(
@@ -534,7 +564,13 @@ class TestGemm8Experimental:
 class TestSlidingWindowKernels:
     """Window-bounded attention vs fp32 torch references (Mistral-family):
     the HIP kernels take a `window` arg and must match the masked refs for
-    contexts beyond the window, across split-context and variant dispatch."""
+    contexts beyond the window, across split-context and variant dispatch.
+
+    Inputs are unscaled randn: with q/k/v scaled by 1/4 attention is almost
+    uniform and a window of W+1 or W-1 moved the prefill outputs by less
+    than the 2e-2 allowance; unscaled, the fp32 reference with W+-1 misses
+    it by 0.08-0.7 (wherever T > W). tests/test_gpu_attention.py holds the
+    cases built to catch off-by-one masks."""
 
     @pytest.mark.parametrize(
         "S,H,Hkv,ctx_max,W",
@@ -576,9 +612,9 @@ class TestSlidingWindowKernels:
 
         H, Hkv, D = 8, 2, 128
         torch.manual_seed(T)
-        q = torch.randn(T, H, D, dtype=torch.bfloat16, device=dev) / 4
-        k = torch.randn(T, Hkv, D, dtype=torch.bfloat16, device=dev) / 4
-        v = torch.randn(T, Hkv, D, dtype=torch.bfloat16, device=dev) / 4
+        q = torch.randn(T, H, D, dtype=torch.bfloat16, device=dev)
+        k = torch.randn(T, Hkv, D, dtype=torch.bfloat16, device=dev)
+        v = torch.randn(T, Hkv, D, dtype=torch.bfloat16, device=dev)
         cu = torch.tensor([0, T], dtype=torch.int32)
         scale = 1.0 / math.sqrt(D)
         got = ops.flash_prefill_varlen(
@@ -597,10 +633,10 @@ class TestSlidingWindowKernels:
         ctx, n_new, W = 150, 30, 48
         torch.manual_seed(7)
         nb = -(-ctx // bs)
-        kc = torch.randn(nb + 1, Hkv, bs, D, dtype=torch.bfloat16, device=dev) / 4
-        vc = torch.randn(nb + 1, Hkv, bs, D, dtype=torch.bfloat16, device=dev) / 4
+        kc = torch.randn(nb + 1, Hkv, bs, D, dtype=torch.bfloat16, device=dev)
+        vc = torch.randn(nb + 1, Hkv, bs, D, dtype=torch.bfloat16, device=dev)
         bt = torch.arange(1, nb + 1, dtype=torch.int32).unsqueeze(0)
-        q = torch.randn(n_new, H, D, dtype=torch.bfloat16, device=dev) / 4
+        q = torch.randn(n_new, H, D, dtype=torch.bfloat16, device=dev)
         cu_q = torch.tensor([0, n_new], dtype=torch.int32)
         cl = torch.tensor([ctx], dtype=torch.int32)
         scale = 1.0 / math.sqrt(D)
