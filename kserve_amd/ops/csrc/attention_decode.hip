@@ -1,15 +1,21 @@
 // Paged attention, decode (single query token per sequence).
 //
 // MI355X-first design (memory-bound KV read; CDNA guide Appendix B):
-//  - workgroup = (seq, kv_head), 4 waves; each wave owns one q head of the
-//    GQA group so the K/V tiles staged in LDS are read once per GROUP, not
-//    once per q head (4x less HBM traffic at group=4).
-//  - KV pages [block=16 tokens][D] staged via 16 B/lane vector loads into
-//    LDS padded to 272 B rows (4-way bank aliasing worst case, G4).
-//  - online softmax in registers; V-phase reads are bank-conflict-free
-//    (lane -> consecutive 4 B within a row).
+//  - workgroup = (kv_head, seq, split), 4 waves; each wave owns one q head
+//    of the GQA group (two at group 5..8). Every wave reads the group's KV
+//    pages [block=16 tokens][D] itself, straight from global memory with
+//    16 B/lane loads: nothing is staged in LDS, and the page reaches HBM
+//    once only as long as the group's waves read it close enough together
+//    for the 32 KiB L1 to still hold it (4 workgroups x 8 KiB page per CU
+//    fill it exactly).
+//  - online softmax and the PV sum in fp32 registers; the only LDS use is
+//    the per-wave broadcast of a page's 16 probabilities.
 //  - split-context (flash-decode style) for small batches: partials
 //    (acc, m, l) to workspace, fused reduction kernel.
+//  - kernels by regime (dispatch at the end of the file): packed-dot "d2"
+//    up to 128 sequences, the wide-V "v4" slot above that
+//    (paged_attention_v4p_kernel, or paged_attention_kernel's V4 path with
+//    KS_ATTN_V4PIPE=0), the generic path for D=64 and groups 5..8.
 //
 // Replaces the vLLM paged-attention path the reference delegates to
 // (SURVEY.md §2.7 row 1).
@@ -22,6 +28,8 @@ namespace {
 
 constexpr int PAGE = 16;      // tokens per KV page
 constexpr int NWAVES = 4;     // waves per workgroup
+// which page loop the wide-V "v4" slot launches when KS_ATTN_V4PIPE is unset
+constexpr bool V4PIPE_DEFAULT = true;
 
 // D: head dim (64 or 128). ACC = D/64 output dims per lane.
 // HPW: q heads per wave (GQA group = NWAVES*HPW covered per workgroup).
@@ -146,10 +154,14 @@ __global__ __launch_bounds__(256, OCC) void paged_attention_kernel(
   for (int a = 0; a < (V4 ? 8 : 1); ++a) acc8[a] = 0.f;
 
   if (!any_active) return;
-  // Direct-global K/V reads, no LDS, no barriers: each page is read once per
-  // workgroup group-wise (4 waves share it through L1/L2); barrier-free
-  // iterations let the compiler keep many loads in flight across pages
-  // (CDNA guide common-mistake #7: don't stage what the cache covers).
+  // Direct-global K/V reads, no LDS staging, no barriers: the 4 waves of a
+  // group share a page through L1/L2 (CDNA guide common-mistake #7: don't
+  // stage what the cache covers). The emitted loop does NOT overlap pages:
+  // each iteration starts with a scalar load of the block id and its
+  // lgkmcnt(0), issues the page's loads, and has consumed them all
+  // (vmcnt(0)) before the next id is fetched; latency is hidden only by the
+  // other resident waves. paged_attention_v4p_kernel is the pipelined form
+  // of the V4 path.
   const int bt_base = (int)((long)seq * max_blocks);
   for (int bi = blk_lo; bi < blk_hi; ++bi) {
     const int block_id = block_tables[bt_base + bi];
@@ -986,6 +998,284 @@ __global__ __launch_bounds__(256) void paged_attention_ws_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Pipelined wide-V kernel (the "v4" slot; KS_ATTN_V4PIPE). Same grid, lane
+// layouts, fp32 softmax/PV and partial format as paged_attention_kernel's
+// V4 path; what differs is how a wave walks its pages:
+//  - block ids: one vector load puts up to 64 table entries of the wave's
+//    page range into a VGPR (lane j <- entry blk_lo + 64*chunk + j); a
+//    page's id comes out with v_readlane, so the per-page loop holds no
+//    load of the table. The next chunk's entries are fetched a whole chunk
+//    ahead.
+//  - register double buffer: the loop is unrolled by two and page i+1's
+//    four K + four V dwordx4 loads are issued into the other register set
+//    before page i's compute, so a wave always has 8-16 loads in flight
+//    (ISA: the next page's K loads, the current page's first multiply
+//    behind s_waitcnt vmcnt(7), the next page's V loads, then counted
+//    waits vmcnt(10)..(8); never vmcnt(0) inside the loop; 126 VGPRs, no
+//    scratch, 4 waves/SIMD, ~188 instructions per page against 212).
+//  - one s_barrier per page pair. Without it the leaner loop lets the
+//    group's waves drift a page apart, the L1 no longer holds the page for
+//    the later waves, and L2 requests rise 10x (TCC_HIT 3.7e7 against
+//    3.9e6 per call at 1536 sequences): slower than the loop it replaces.
+//    With it the waves issue the same loads together and the L1 serves
+//    three of the four. Waves without a q head (group < 4) run the same
+//    number of barriers and nothing else.
+//  - every table index (prefetch and refill) is clamped to blk_hi - 1: the
+//    entry after the range may lie past the table, and the block it names
+//    need not exist. The clamp re-reads the last page; its data is not used.
+//  - same bits: the output is bit-for-bit what the V4 path of
+//    paged_attention_kernel gives (0 of 6.3M outputs differ at 1536
+//    sequences), so switching loops does not change a served token. Every
+//    fp32 rounding is therefore kept in that kernel's order: the QK dot as
+//    the even/odd packed-FMA chain the compiler made of its 32-term sum,
+//    the xor-2 then xor-1 quad sum, the xor 4/8/16/32 butterfly for the sum
+//    of p, fma(l, rescale, psum), acc * rescale then one fma per token. A
+//    v_dot2_f32_bf16 dot and a sum of p deferred to the epilogue were
+//    faster still (152 instructions per page, 108 VGPRs) but flipped bf16
+//    near-ties downstream, and were dropped for that.
+//  - cross-lane steps stay off the LDS crossbar: DPP quad_perm for the
+//    4-lane dot, DPP row_ror 4/8 (max) and row_half_mirror/row_mirror (sum,
+//    same partners as xor 4/8 on 4-lane-uniform values) within a row, then
+//    v_permlane16_swap + v_permlane32_swap across the 4 rows.
+//  - p reaches the V layout through LDS as before, stored transposed so the
+//    lane's four values are one ds_read_b128.
+// ---------------------------------------------------------------------------
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL,
+                                         0xf, 0xf, true));
+}
+constexpr int DPP_QUAD_XOR1 = 0xB1;  // quad_perm:[1,0,3,2]
+constexpr int DPP_QUAD_XOR2 = 0x4E;  // quad_perm:[2,3,0,1]
+constexpr int DPP_ROW_ROR4 = 0x124;
+constexpr int DPP_ROW_ROR8 = 0x128;
+constexpr int DPP_ROW_MIRROR = 0x140;
+constexpr int DPP_ROW_HALF_MIRROR = 0x141;
+
+// lane i of every 16-lane row <- op over lane i of the 4 rows
+__device__ __forceinline__ float rows_max(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  v = fmaxf(__builtin_bit_cast(float, (unsigned)r[0]),
+            __builtin_bit_cast(float, (unsigned)r[1]));
+  const unsigned w = __builtin_bit_cast(unsigned, v);
+  r = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+  return fmaxf(__builtin_bit_cast(float, (unsigned)r[0]),
+               __builtin_bit_cast(float, (unsigned)r[1]));
+}
+__device__ __forceinline__ float rows_sum(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  v = __builtin_bit_cast(float, (unsigned)r[0]) +
+      __builtin_bit_cast(float, (unsigned)r[1]);
+  const unsigned w = __builtin_bit_cast(unsigned, v);
+  r = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+  return __builtin_bit_cast(float, (unsigned)r[0]) +
+         __builtin_bit_cast(float, (unsigned)r[1]);
+}
+
+__global__ __launch_bounds__(256) void paged_attention_v4p_kernel(
+    short* __restrict__ out, const short* __restrict__ q,
+    const short* __restrict__ k_cache, const short* __restrict__ v_cache,
+    const int* __restrict__ block_tables, const int* __restrict__ context_lens,
+    const float scale, const int num_kv_heads, const int group,
+    const int max_blocks, const long q_row_stride, const int n_splits,
+    float* __restrict__ part_out, float* __restrict__ part_ml,
+    const int window) {
+  constexpr int D = 128;
+  constexpr int QFRAG = D / 4;
+  const int kv_head = blockIdx.x;
+  const int seq = blockIdx.y;
+  const int split = blockIdx.z;
+  const int ctx = context_lens[seq];
+  if (ctx <= 0) return;
+  const int num_heads = num_kv_heads * group;
+  const int lane = threadIdx.x & 63;
+  // wave-uniform by construction: the idle-wave branch below holds
+  // barriers and must be a scalar branch, not an exec-masked region
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tok = lane >> 2;   // QK: token within the page
+  const int part = lane & 3;   // QK: quarter of D
+  const int vtok = lane >> 4;  // PV: tokens vtok, 4+vtok, 8+vtok, 12+vtok
+  const int vdim = (lane & 15) * 8;
+  __shared__ __attribute__((aligned(16))) float p_bc[NWAVES][PAGE];
+
+  const int nblocks = (ctx + PAGE - 1) / PAGE;
+  // sliding window: only pages holding the last `window` tokens are read
+  const int wstart = (window > 0 && ctx > window) ? ctx - window : 0;
+  const int first_blk = wstart / PAGE;
+  const int blocks_per_split =
+      (nblocks - first_blk + n_splits - 1) / n_splits;
+  const int blk_lo = first_blk + split * blocks_per_split;
+  const int blk_hi = min(nblocks, blk_lo + blocks_per_split);
+  if (blk_lo >= blk_hi) {
+    // record empty partial so the reducer can skip it
+    if (n_splits > 1 && threadIdx.x < (unsigned)group) {
+      const int h = kv_head * group + threadIdx.x;
+      float* ml = part_ml + (((long)seq * num_heads + h) * n_splits + split) * 2;
+      ml[0] = NEG_INF;
+      ml[1] = 0.f;
+    }
+    return;
+  }
+  const int npages = blk_hi - blk_lo;
+  if (wave >= group) {
+    // a wave without a q head (group < 4) reads nothing; it only meets the
+    // working waves at their per-page-pair barriers
+    for (int i = 0; i < npages; i += 2) __builtin_amdgcn_s_barrier();
+    return;
+  }
+  const int head = kv_head * group + wave;
+
+  float q_frag[QFRAG];
+  {
+    const short* qp =
+        q + (long)seq * q_row_stride + (long)head * D + part * QFRAG;
+#pragma unroll
+    for (int j = 0; j < QFRAG; ++j) q_frag[j] = bf16_bits_to_float(qp[j]);
+  }
+
+  const int* bt_row = block_tables + (long)seq * max_blocks + blk_lo;
+  // lane j <- table entry of page c0 + j, never past the range's last
+  auto load_ids = [&](int c0) {
+    return bt_row[min(c0 + lane, npages - 1)];
+  };
+  // per-lane element offsets inside a page
+  const int k_off = tok * D + part * QFRAG;
+  const int v_off = vtok * D + vdim;
+  const long head_off = (long)kv_head * PAGE * D;
+  const long blk_stride = (long)num_kv_heads * PAGE * D;
+  auto load_page = [&](int block_id, short8_t* kreg, short8_t* vreg) {
+    const long pbase = (long)block_id * blk_stride + head_off;
+    const short8_t* kp =
+        reinterpret_cast<const short8_t*>(k_cache + pbase + k_off);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) kreg[c] = kp[c];
+    const short* vp = v_cache + pbase + v_off;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4)
+      vreg[q4] = *reinterpret_cast<const short8_t*>(vp + q4 * 4 * D);
+  };
+
+  float m = NEG_INF;
+  float l = 0.f;
+  float acc8[8];
+#pragma unroll
+  for (int a = 0; a < 8; ++a) acc8[a] = 0.f;
+  float* pw = &p_bc[wave][(tok & 3) * 4 + (tok >> 2)];
+  const float4_t* pr = reinterpret_cast<const float4_t*>(&p_bc[wave][vtok * 4]);
+
+  auto compute_page = [&](int bi, const short8_t* kreg,
+                          const short8_t* vreg) {
+    // Every rounding below is pinned to what paged_attention_kernel's V4
+    // path computes as built (header: "same bits"), so nothing here may be
+    // reassociated: explicit fmaf, and the even/odd dot in the packed-FMA
+    // order the compiler gave the old loop's 32-term sum.
+#pragma clang fp reassociate(off)
+    float lo = 0.f, hi = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int r = i & 3, g = i >> 2;
+      const int c = r == 0 ? 1 : (r == 1 ? 0 : r);               // 1,0,2,3
+      const int w = g == 0 ? 2 : (g == 1 ? 0 : (g == 2 ? 3 : 1));  // 2,0,3,1
+      const float kl = bf16_bits_to_float(kreg[c][2 * w]);
+      const float kh = bf16_bits_to_float(kreg[c][2 * w + 1]);
+      const float ql = q_frag[c * 8 + 2 * w], qh = q_frag[c * 8 + 2 * w + 1];
+      lo = i == 0 ? ql * kl : __builtin_fmaf(ql, kl, lo);
+      hi = i == 0 ? qh * kh : __builtin_fmaf(qh, kh, hi);
+    }
+    float s = lo + hi;
+    s += dpp_mov<DPP_QUAD_XOR2>(s);
+    s += dpp_mov<DPP_QUAD_XOR1>(s);
+    const int gtok = bi * PAGE + tok;
+    s = (gtok < ctx && gtok >= wstart) ? s * scale : NEG_INF;
+    // s is uniform within each 4-lane token group: rotating a row by 4 and
+    // 8 lanes covers its 4 tokens, the two swaps cover the 4 rows
+    float tmax = fmaxf(s, dpp_mov<DPP_ROW_ROR4>(s));
+    tmax = fmaxf(tmax, dpp_mov<DPP_ROW_ROR8>(tmax));
+    tmax = rows_max(tmax);
+    const float m_new = fmaxf(m, tmax);
+    const float rescale = __expf(m - m_new);
+    const float p = (s > NEG_INF) ? __expf(s - m_new) : 0.f;
+    // the old loop's xor-4/8/16/32 butterfly: p is uniform within 4-lane
+    // groups, so mirroring a half row swaps the same partners as xor 4 and
+    // mirroring the row after it the same sums as xor 8
+    float psum = p + dpp_mov<DPP_ROW_HALF_MIRROR>(p);
+    psum += dpp_mov<DPP_ROW_MIRROR>(psum);
+    psum = rows_sum(psum);
+    l = __builtin_fmaf(l, rescale, psum);
+    m = m_new;
+    // same-wave LDS broadcast of p into the V layout; DS ops of one wave
+    // complete in order, the fences only pin the compiler's order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    if (part == 0) *pw = p;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const float4_t pt4 = *pr;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int a = 0; a < 8; ++a) acc8[a] *= rescale;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const float pt = pt4[q4];
+#pragma unroll
+      for (int a = 0; a < 8; ++a)
+        acc8[a] = __builtin_fmaf(pt, bf16_bits_to_float(vreg[q4][a]), acc8[a]);
+    }
+  };
+
+  short8_t kA[4], vA[4], kB[4], vB[4];
+  int ids_next = load_ids(0);
+  load_page(__builtin_amdgcn_readlane(ids_next, 0), kA, vA);
+  for (int c0 = 0; c0 < npages; c0 += 64) {
+    const int ids = ids_next;
+    ids_next = load_ids(c0 + 64);
+    const int cn = min(64, npages - c0);
+    for (int j = 0; j < cn; j += 2) {
+      // the group's waves issue the same two pages' loads together (see
+      // the header); (npages + 1) / 2 barriers in all, as for idle waves
+      __builtin_amdgcn_s_barrier();
+      // page j+1 (or the last page again) into B, then compute A
+      load_page(__builtin_amdgcn_readlane(ids, min(j + 1, cn - 1)), kB, vB);
+      compute_page(blk_lo + c0 + j, kA, vA);
+      // page j+2 into A: this chunk's, the next chunk's first, or the
+      // range's last again (ids_next is clamped the same way)
+      const int id_a = __builtin_amdgcn_readlane(ids, min(j + 2, cn - 1));
+      const int id_n = __builtin_amdgcn_readlane(ids_next, 0);
+      load_page(j + 2 < 64 ? id_a : id_n, kA, vA);
+      if (j + 1 < cn) compute_page(blk_lo + c0 + j + 1, kB, vB);
+    }
+  }
+
+  // cross token-slice reduction (deferred from the per-page PV): lanes
+  // sharing lane%16 hold 4-token partials of the same 8 dims
+#pragma unroll
+  for (int a = 0; a < 8; ++a) acc8[a] = rows_sum(acc8[a]);
+  if (n_splits == 1) {
+    const float inv_l = (l > 0.f) ? 1.f / l : 0.f;
+    if (lane < 16) {
+      short* op = out + ((long)seq * num_heads + head) * D + vdim;
+#pragma unroll
+      for (int a = 0; a < 8; ++a) op[a] = float_to_bf16_bits(acc8[a] * inv_l);
+    }
+  } else {
+    if (lane < 16) {
+      float* po = part_out +
+                  (((long)seq * num_heads + head) * n_splits + split) * D +
+                  vdim;
+#pragma unroll
+      for (int a = 0; a < 8; ++a) po[a] = acc8[a];
+    }
+    if (lane == 0) {
+      float* ml =
+          part_ml + (((long)seq * num_heads + head) * n_splits + split) * 2;
+      ml[0] = m;
+      ml[1] = l;
+    }
+  }
+}
+
 // Combine split-context partials: one wave per (seq, head); lane owns D/64
 // dims across all splits.
 template <int D>
@@ -1215,8 +1505,24 @@ extern "C" hipError_t ks_paged_attention_decode(
     const char* e = getenv("KS_ATTN_V4D2");
     return e != nullptr && e[0] == '1';
   }();
+  // the v4 slot's page loop: KS_ATTN_V4PIPE=1 the pipelined kernel
+  // (register double buffer, block ids by readlane, DPP/permlane
+  // reductions, one barrier per page pair), =0 the one-page-at-a-time loop
+  // of paged_attention_kernel;
+  // unset takes V4PIPE_DEFAULT (measurements: profiles/attn_decode_bench.md)
+  static const bool v4_pipe = [] {
+    const char* e = getenv("KS_ATTN_V4PIPE");
+    return e ? e[0] == '1' : V4PIPE_DEFAULT;
+  }();
   if (use_v4 && hpw == 1 && head_dim == 128) {
-    if (v4_d2) {
+    if (v4_pipe && !v4_d2) {
+      hipLaunchKernelGGL(
+          paged_attention_v4p_kernel, grid, block, 0, stream, (short*)out,
+          (const short*)q, (const short*)k_cache, (const short*)v_cache,
+          (const int*)block_tables, (const int*)context_lens, scale,
+          num_kv_heads, group, max_blocks, q_row_stride, n_splits,
+          (float*)part_out, (float*)part_ml, window);
+    } else if (v4_d2) {
       hipLaunchKernelGGL(
           (paged_attention_kernel<128, 1, 1, true, true, true>), grid, block,
           0, stream, (short*)out, (const short*)q, (const short*)k_cache,

@@ -187,6 +187,9 @@ void paged_attention_decode(at::Tensor& out, at::Tensor& q,
   CHECK_KV_CACHE(v_cache);
   TORCH_CHECK(block_tables.scalar_type() == at::kInt, "block_tables int32");
   TORCH_CHECK(context_lens.scalar_type() == at::kInt, "context_lens int32");
+  // the kernels index both as dense arrays (row stride = size(1))
+  TORCH_CHECK(block_tables.is_contiguous(), "block_tables must be contiguous");
+  TORCH_CHECK(context_lens.is_contiguous(), "context_lens must be contiguous");
   const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
   int S = q.size(0);
   int H = q.size(1);

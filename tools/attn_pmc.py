@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Decode-attention PMC target: repeated V4-path launches at the headline
-shape (S=256, ctx=576) for rocprofv3 --pmc."""
+"""Decode-attention PMC target: repeated V4-path launches at S x ctx=576
+(S=256, or KS_ATTN_PMC_S: 1536 is the batch bench.py runs) for
+rocprofv3 --pmc."""
 import math
 import os
 import sys
@@ -12,7 +13,8 @@ from kserve_amd import ops
 
 dev = "cuda:0"
 torch.manual_seed(0)
-S, H, Hkv, ctx, D, bs = 256, 32, 8, 576, 128, 16
+S = int(os.environ.get("KS_ATTN_PMC_S", "256"))
+H, Hkv, ctx, D, bs = 32, 8, 576, 128, 16
 nb = (ctx + bs - 1) // bs
 B = S * nb + 1
 kc = torch.randn(B, Hkv, bs, D, dtype=torch.bfloat16, device=dev)
