@@ -262,6 +262,16 @@ class ParallelConfig:
 
 
 @dataclass
+class LoRAConfig:
+    """Capacity of the stacked adapter storage behind the batched decode
+    kernels (engine/lora.py). Fixed at the first registration: the stacks
+    never move afterwards, so captured decode graphs stay valid."""
+
+    max_loras: int = 8       # adapter slots
+    max_lora_rank: int = 64  # largest adapter rank accepted
+
+
+@dataclass
 class EngineConfig:
     model: ModelConfig = field(default_factory=ModelConfig.llama3_8b)
     cache: CacheConfig = field(default_factory=CacheConfig)
@@ -278,3 +288,4 @@ class EngineConfig:
     draft_model: Optional[ModelConfig] = None
     draft_model_path: Optional[str] = None
     eos_token_id: int = 128001
+    lora: LoRAConfig = field(default_factory=LoRAConfig)

@@ -305,9 +305,9 @@ class LLMEngine:
             )
         return self._guided_json
 
-    def register_lora(self, name: str, path: str) -> int:
-        """Load a PEFT adapter and make it addressable by name (reference:
-        --lora-modules name=path registering adapter model names)."""
+    def get_lora_manager(self):
+        """The engine's LoRAManager, created on first use with the stack
+        capacity of ``config.lora``."""
         if self.lora_manager is None:
             from kserve_amd.engine.lora import LoRAManager
 
@@ -317,9 +317,16 @@ class LLMEngine:
                 self.model.dtype,
                 tp_rank=st.tp_rank,
                 tp_size=st.tp_size,
+                max_loras=self.config.lora.max_loras,
+                max_lora_rank=self.config.lora.max_lora_rank,
             )
             self.runner.lora_manager = self.lora_manager
-        return self.lora_manager.register(name, path)
+        return self.lora_manager
+
+    def register_lora(self, name: str, path: str) -> int:
+        """Load a PEFT adapter and make it addressable by name (reference:
+        --lora-modules name=path registering adapter model names)."""
+        return self.get_lora_manager().register(name, path)
 
     def abort_request(self, request_id: str):
         self.scheduler.abort_request(request_id)

@@ -45,6 +45,11 @@ class ModelRunner:
         # sampled-decode variants: same buckets, sampler inside the graph
         # (captured lazily on first temperature>0 window; shares the pool)
         self._sampled_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        # multi-LoRA decode variants: same buckets, the batched adapter
+        # kernels inside the graph reading the static lora_slots buffer
+        # (captured lazily the first time a bucket sees an adapter request)
+        self._lora_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self._lora_graphs_version = -1
         self._graph_pool = None
         self._graph_buffers: Optional[Dict[str, torch.Tensor]] = None
         self._graph_batch_sizes: List[int] = []
@@ -293,6 +298,9 @@ class ModelRunner:
                 "positions": torch.empty(cap, dtype=torch.int64, pin_memory=pin),
                 "slot_mapping": torch.empty(cap, dtype=torch.int32, pin_memory=pin),
                 "context_lens": torch.empty(cap, dtype=torch.int32, pin_memory=pin),
+                "lora_slots": torch.full(
+                    (cap,), -1, dtype=torch.int32, pin_memory=pin
+                ),
                 "block_tables": torch.zeros(
                     (cap, mb), dtype=torch.int32, pin_memory=pin
                 ),
@@ -359,12 +367,14 @@ class ModelRunner:
         return input_ids, pos, meta
 
     def _lora_meta(self, batch: ScheduledBatch, per_request_rows: bool):
-        """Contiguous (adapter_id, start_row, end_row) segments for the batch.
-        Prefill rows span each request's scheduled tokens; decode rows are one
-        per request."""
+        """Contiguous (adapter_id, start_row, end_row) segments for the batch
+        and ``row_slots``, the [T] int32 adapter slot (``lora_id - 1``, -1
+        for base rows) of every row. Prefill rows span each request's
+        scheduled tokens; decode rows are one per request."""
         from kserve_amd.engine.lora import LoRABatchMeta
 
         segments = []
+        slots: List[int] = []
         row = 0
         cur_id, cur_start = None, 0
         widths = (
@@ -378,9 +388,17 @@ class ModelRunner:
                     segments.append((cur_id, cur_start, row))
                 cur_id, cur_start = req.lora_id, row
             row += w
+            slots.extend([req.lora_id - 1] * w)
         if cur_id:
             segments.append((cur_id, cur_start, row))
-        return LoRABatchMeta(segments, self.lora_manager)
+        row_slots = torch.tensor(slots, dtype=torch.int32)
+        if per_request_rows:
+            # only decode steps read it on the device (batched kernels)
+            row_slots = row_slots.to(self.device)
+        return LoRABatchMeta(
+            segments, self.lora_manager, row_slots=row_slots,
+            decode=per_request_rows,
+        )
 
     # -- execution ----------------------------------------------------------
     @torch.no_grad()
@@ -397,10 +415,16 @@ class ModelRunner:
     def execute_decode(self, batch, block_manager) -> torch.Tensor:
         n = len(batch.requests)
         has_lora = any(r.lora_id for r in batch.requests)
-        if self._graphs and not self.config.enforce_eager and not has_lora:
+        if (
+            self._graphs
+            and not self.config.enforce_eager
+            and (not has_lora or self._lora_graphable())
+        ):
             bucket = self._graph_bucket(n)
             if bucket is not None:
-                return self._run_graph(bucket, batch, block_manager)
+                return self._run_graph(
+                    bucket, batch, block_manager, lora=has_lora
+                )
         input_ids, positions, meta = self.prepare_decode(batch, block_manager)
         if has_lora:
             meta.lora = self._lora_meta(batch, per_request_rows=True)
@@ -485,6 +509,12 @@ class ModelRunner:
                 (max_bs, mb), dtype=torch.int32, device=dev
             ),
             "context_lens": torch.ones(max_bs, dtype=torch.int32, device=dev),
+            # LoRA decode graphs: per-row adapter slot (-1 = base) and the
+            # KV slot mapping staged from the host
+            "lora_slots": torch.full(
+                (max_bs,), -1, dtype=torch.int32, device=dev
+            ),
+            "slot_mapping": torch.zeros(max_bs, dtype=torch.int32, device=dev),
             # per-request sampling params (sampled-window variants)
             "temps": torch.ones(max_bs, dtype=torch.float32, device=dev),
             "top_p": torch.ones(max_bs, dtype=torch.float32, device=dev),
@@ -598,13 +628,89 @@ class ModelRunner:
         logger.info("Captured sampled-decode hipGraph for batch size %d", bs)
         return g
 
+    def _lora_graphable(self) -> bool:
+        """LoRA decode can replay a graph when the adapters sit in the
+        manager's stacks and the batched kernels are not switched off."""
+        from kserve_amd.engine.lora import batched_decode_enabled
+
+        return (
+            self.lora_manager is not None
+            and self.lora_manager.has_stacks
+            and batched_decode_enabled()
+        )
+
+    def _ensure_lora_graph(self, bs: int) -> torch.cuda.CUDAGraph:
+        """Capture (once, lazily) the multi-LoRA decode variant for a
+        bucket: the decode forward with ``meta.lora`` reading the static
+        ``lora_slots`` buffer, so the adapter mix is device data and a
+        replay serves any mix. The adapter stacks are written in place by
+        later registrations, which therefore reach this graph; only a
+        registration that adds a stack for a module no earlier adapter
+        targeted makes the captured graphs stale (they hold no launches for
+        it) and drops them."""
+        from kserve_amd.engine.lora import LoRABatchMeta
+
+        mgr = self.lora_manager
+        if self._lora_graphs_version != mgr.stacks_version:
+            self._lora_graphs.clear()
+            self._lora_graphs_version = mgr.stacks_version
+        g = self._lora_graphs.get(bs)
+        if g is not None:
+            return g
+        buf = self._graph_buffers
+
+        def body():
+            # One step per replay: multi-step windows do not take adapter
+            # batches yet, so the in-graph slot derivation and the sampled
+            # token feedback of the base graph (about ten small kernels
+            # that only windows need) are left out. The slot mapping comes
+            # staged from the host like the other inputs.
+            meta = AttentionMetadata(
+                is_prefill=False,
+                slot_mapping=buf["slot_mapping"][:bs],
+                block_tables=buf["block_tables"][:bs],
+                context_lens=buf["context_lens"][:bs],
+            )
+            meta.lora = LoRABatchMeta(
+                [], mgr, row_slots=buf["lora_slots"][:bs], decode=True
+            )
+            hidden = self.model(
+                buf["input_ids"][:bs], buf["positions"][:bs],
+                self.kv_caches, meta,
+            )
+            return self.model.compute_logits(hidden)
+
+        # the warm-up run really executes on whatever the static buffers
+        # hold: run it as all-padding (scratch block 0, base-model rows) so
+        # it writes no live KV page, then let the caller stage real inputs
+        buf["input_ids"][:bs].zero_()
+        buf["positions"][:bs].zero_()
+        buf["context_lens"][:bs].fill_(1)
+        buf["block_tables"][:bs].zero_()
+        buf["slot_mapping"][:bs].zero_()
+        buf["lora_slots"][:bs].fill_(-1)
+        body()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._graph_pool):
+            logits = body()
+        self._lora_graphs[bs] = g
+        buf.setdefault("lora_logits", {})[bs] = logits
+        logger.info("Captured multi-LoRA decode hipGraph for batch size %d", bs)
+        return g
+
     def _graph_bucket(self, n: int) -> Optional[int]:
         for b in self._graph_batch_sizes:
             if b >= n:
                 return b
         return None
 
-    def _run_graph(self, bucket: int, batch, block_manager) -> torch.Tensor:
+    def _run_graph(
+        self, bucket: int, batch, block_manager, lora: bool = False
+    ) -> torch.Tensor:
+        if lora:
+            # before staging: the capture's warm-up run uses the buffers
+            graph = self._ensure_lora_graph(bucket)
         n, nb = self._fill_pinned(batch, block_manager)
         pin = self._pin
         pnp = self._pin_np
@@ -625,6 +731,16 @@ class ModelRunner:
         buf["block_tables"][:bucket, :nb].copy_(
             pin["block_tables"][:bucket, :nb], non_blocking=True
         )
+        if lora:
+            ls = pnp["lora_slots"]
+            for i, req in enumerate(batch.requests):
+                ls[i] = req.lora_id - 1
+            ls[n:bucket] = -1  # padding rows: base model
+            pnp["slot_mapping"][n:bucket] = 0  # scratch block 0, offset 0
+            for key in ("lora_slots", "slot_mapping"):
+                buf[key][:bucket].copy_(pin[key][:bucket], non_blocking=True)
+            graph.replay()
+            return buf["lora_logits"][bucket][:n]
         self._graphs[bucket].replay()
         return buf["logits"][bucket][:n]
 

@@ -410,3 +410,49 @@ def topk_topp_sample_into(
         seeds,
     )
     return out
+
+
+def lora_shrink(
+    x: torch.Tensor,
+    a_stack: torch.Tensor,
+    ranks: torch.Tensor,
+    slot_idx: torch.Tensor,
+) -> torch.Tensor:
+    """Batched multi-LoRA shrink (BGMV): tmp[t, :rr] = x[t] @ A[slot_t, :rr]^T.
+
+    x [T, K] bf16 rows (row stride allowed), a_stack [S, R, K] bf16, ranks
+    [S] int32, slot_idx [T] int32 on the device; rr = round_up(ranks[slot],
+    8). Returns fp32 [T, R]; on the GPU, rows whose slot is outside [0, S)
+    and columns at or past rr are left unwritten (lora_expand_add reads
+    neither)."""
+    if x.is_cuda:
+        tmp = torch.empty(
+            (x.shape[0], a_stack.shape[1]), dtype=torch.float32, device=x.device
+        )
+        _native("lora_shrink").lora_shrink(tmp, x, a_stack, ranks, slot_idx)
+        return tmp
+    return torch_ref.lora_shrink(x, a_stack, ranks, slot_idx)
+
+
+def lora_expand_add(
+    y: torch.Tensor,
+    tmp: torch.Tensor,
+    b_stack: torch.Tensor,
+    scale: torch.Tensor,
+    ranks: torch.Tensor,
+    slot_idx: torch.Tensor,
+    out_offset: int = 0,
+) -> torch.Tensor:
+    """Batched multi-LoRA expand, in place:
+    y[t, off:off+N] += scale[slot_t] * tmp[t, :rr] @ B[slot_t, :, :rr]^T,
+    fp32 accumulate, rounded once. y may be a strided view of a wider row;
+    columns outside [off, off+N) and rows whose slot is outside [0, S) keep
+    their bits."""
+    if y.is_cuda:
+        _native("lora_expand_add").lora_expand_add(
+            y, tmp, b_stack, scale, ranks, slot_idx, int(out_offset)
+        )
+        return y
+    return torch_ref.lora_expand_add(
+        y, tmp, b_stack, scale, ranks, slot_idx, out_offset
+    )

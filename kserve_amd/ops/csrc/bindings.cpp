@@ -62,6 +62,11 @@ hipError_t ks_skinny_gemm_w8(void*, void*, const void*, const void*,
                              const void*, int, int, int, long, hipStream_t);
 hipError_t ks_dequant_fp8_rows(void*, const void*, const void*, long, int,
                                hipStream_t);
+hipError_t ks_lora_shrink(void*, const void*, const void*, const void*,
+                          const void*, int, int, int, int, long, hipStream_t);
+hipError_t ks_lora_expand_add(void*, const void*, const void*, const void*,
+                              const void*, const void*, int, int, int, int,
+                              long, int, hipStream_t);
 }
 
 namespace {
@@ -464,6 +469,91 @@ void dequant_fp8_rows(at::Tensor& out, at::Tensor& qweight,
             "dequant_fp8_rows");
 }
 
+// [T, cols] bf16 rows of a possibly wider buffer: unit inner stride, every
+// row start 16-byte aligned (the LoRA kernels use 16 B / 8 B vectors)
+#define CHECK_LORA_ROWS(t)                                                 \
+  TORCH_CHECK((t).scalar_type() == at::kBFloat16 && (t).is_cuda() &&       \
+                  (t).dim() == 2,                                          \
+              #t " must be a 2-D bf16 GPU tensor");                        \
+  TORCH_CHECK((t).stride(1) == 1, #t " must have unit inner stride");      \
+  TORCH_CHECK((t).size(0) <= 1 || (t).stride(0) % 8 == 0,                  \
+              #t " row stride must be a multiple of 8 elements");          \
+  TORCH_CHECK(reinterpret_cast<uintptr_t>((t).data_ptr()) % 16 == 0,       \
+              #t " rows must be 16-byte aligned")
+
+// stacks [S, rows, cols] bf16, per-slot scale/ranks, per-row slot index
+void check_lora_meta(const at::Tensor& stack, const at::Tensor& ranks,
+                     const at::Tensor& slot_idx, int64_t T) {
+  TORCH_CHECK(stack.scalar_type() == at::kBFloat16 && stack.is_cuda() &&
+                  stack.dim() == 3,
+              "adapter stack must be a 3-D bf16 GPU tensor");
+  TORCH_CHECK(stack.is_contiguous(), "adapter stack must be contiguous");
+  TORCH_CHECK(ranks.scalar_type() == at::kInt && ranks.is_cuda() &&
+                  ranks.is_contiguous() && ranks.dim() == 1 &&
+                  ranks.size(0) == stack.size(0),
+              "ranks must be a contiguous int32 [S] GPU tensor");
+  TORCH_CHECK(slot_idx.scalar_type() == at::kInt && slot_idx.is_cuda() &&
+                  slot_idx.dim() == 1 && slot_idx.size(0) == T,
+              "slot_idx must be an int32 [T] GPU tensor");
+  TORCH_CHECK(slot_idx.is_contiguous(), "slot_idx must be contiguous");
+  TORCH_CHECK(T <= 65535, "at most 65535 rows per call");
+}
+
+void lora_shrink(at::Tensor& tmp, at::Tensor& x, at::Tensor& a_stack,
+                 at::Tensor& ranks, at::Tensor& slot_idx) {
+  // tmp [T, R] f32 <- x [T, K] bf16 . a_stack[slot_idx] [R, K]^T, rows with
+  // a slot outside [0, S) skipped
+  CHECK_LORA_ROWS(x);
+  const int64_t T = x.size(0), K = x.size(1);
+  check_lora_meta(a_stack, ranks, slot_idx, T);
+  const int64_t S = a_stack.size(0), R = a_stack.size(1);
+  TORCH_CHECK(a_stack.size(2) == K, "a_stack must be [S, R, K]");
+  TORCH_CHECK(K > 0 && K % 64 == 0, "lora_shrink needs K % 64 == 0");
+  TORCH_CHECK(R > 0 && R % 8 == 0, "lora_shrink needs R % 8 == 0");
+  TORCH_CHECK(tmp.scalar_type() == at::kFloat && tmp.is_cuda() &&
+                  tmp.is_contiguous() && tmp.dim() == 2 && tmp.size(0) == T &&
+                  tmp.size(1) == R,
+              "tmp must be a contiguous f32 [T, R] GPU tensor");
+  check_hip(ks_lora_shrink(tmp.data_ptr(), x.data_ptr(), a_stack.data_ptr(),
+                           slot_idx.data_ptr(), ranks.data_ptr(), (int)T,
+                           (int)K, (int)R, (int)S,
+                           T > 1 ? (long)x.stride(0) : 0L,
+                           current_stream()),
+            "lora_shrink");
+}
+
+void lora_expand_add(at::Tensor& y, at::Tensor& tmp, at::Tensor& b_stack,
+                     at::Tensor& scale, at::Tensor& ranks,
+                     at::Tensor& slot_idx, int64_t off) {
+  // y[:, off:off+N] bf16 += scale[slot] * tmp [T, R] f32 . b_stack[slot]
+  // [N, R]^T, in place, one rounding; rows with a slot outside [0, S) and
+  // columns outside [off, off+N) untouched
+  CHECK_LORA_ROWS(y);
+  const int64_t T = y.size(0);
+  check_lora_meta(b_stack, ranks, slot_idx, T);
+  const int64_t S = b_stack.size(0), N = b_stack.size(1), R = b_stack.size(2);
+  TORCH_CHECK(N > 0 && N % 64 == 0, "lora_expand_add needs N % 64 == 0");
+  TORCH_CHECK(R > 0 && R % 8 == 0, "lora_expand_add needs R % 8 == 0");
+  TORCH_CHECK(off >= 0 && off % 8 == 0,
+              "out_offset must be a non-negative multiple of 8");
+  TORCH_CHECK(off + N <= y.size(1), "out_offset + N exceeds the row of y");
+  TORCH_CHECK(tmp.scalar_type() == at::kFloat && tmp.is_cuda() &&
+                  tmp.is_contiguous() && tmp.dim() == 2 && tmp.size(0) == T &&
+                  tmp.size(1) == R,
+              "tmp must be a contiguous f32 [T, R] GPU tensor");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_cuda() &&
+                  scale.is_contiguous() && scale.dim() == 1 &&
+                  scale.size(0) == S,
+              "scale must be a contiguous f32 [S] GPU tensor");
+  check_hip(ks_lora_expand_add(y.data_ptr(), tmp.data_ptr(),
+                               b_stack.data_ptr(), scale.data_ptr(),
+                               slot_idx.data_ptr(), ranks.data_ptr(), (int)T,
+                               (int)N, (int)R, (int)S,
+                               T > 1 ? (long)y.stride(0) : 0L,
+                               (int)off, current_stream()),
+            "lora_expand_add");
+}
+
 void gemm8(at::Tensor& d, at::Tensor& a, at::Tensor& w, int64_t swizzle) {
   // EXPERIMENTAL (see gemm8.hip header): not used by ops.linear dispatch
   CHECK_BF16_CONTIG(d);
@@ -515,6 +605,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "decode GEMM, fp8 e4m3 weights x bf16 activations (N<=256)");
   m.def("dequant_fp8_rows", &dequant_fp8_rows,
         "fp8 e4m3 rows * per-row scale -> bf16");
+  m.def("lora_shrink", &lora_shrink,
+        "batched multi-LoRA shrink: tmp = x . A[slot]^T per row (f32 out)");
+  m.def("lora_expand_add", &lora_expand_add,
+        "batched multi-LoRA expand: y += scale[slot] * tmp . B[slot]^T per row",
+        pybind11::arg("y"), pybind11::arg("tmp"), pybind11::arg("b_stack"),
+        pybind11::arg("scale"), pybind11::arg("ranks"),
+        pybind11::arg("slot_idx"), pybind11::arg("out_offset") = 0);
   m.def("gemm8", &gemm8,
         "EXPERIMENTAL 8-phase 256x256 MFMA GEMM (round-2 candidate)");
   m.def("mfma_probe", &mfma_probe, "MFMA layout probe (tests)");

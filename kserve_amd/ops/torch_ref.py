@@ -325,3 +325,57 @@ def linear_w8(
     if bias is not None:
         y = y + bias.float()
     return y.to(x.dtype)
+
+
+def _lora_rows_by_slot(slot_idx: torch.Tensor, ranks: torch.Tensor, R: int):
+    """Yield (slot, rr, rows) for every slot in [0, S) some row references;
+    rows with a slot outside that range are skipped, as in the kernels."""
+    S = ranks.shape[0]
+    slots = slot_idx.to(torch.int64)
+    for s in torch.unique(slots).tolist():
+        if s < 0 or s >= S:
+            continue
+        rr = min(R, (max(int(ranks[s]), 0) + 7) // 8 * 8)
+        yield s, rr, torch.nonzero(slots == s).squeeze(1)
+
+
+def lora_shrink(
+    x: torch.Tensor,        # [T, K]
+    a_stack: torch.Tensor,  # [S, R, K]
+    ranks: torch.Tensor,    # [S] int32
+    slot_idx: torch.Tensor,  # [T] int32
+) -> torch.Tensor:
+    """Batched multi-LoRA shrink, fp32 reference: per row t,
+    tmp[t, :rr] = x[t] @ a_stack[slot_t, :rr]^T with rr = round_up(rank, 8).
+    Rows whose slot is outside [0, S) and columns at or past rr stay 0 (the
+    kernel leaves them unwritten). Returns fp32 [T, R]."""
+    R = a_stack.shape[1]
+    tmp = torch.zeros(x.shape[0], R, dtype=torch.float32, device=x.device)
+    for s, rr, rows in _lora_rows_by_slot(slot_idx, ranks, R):
+        tmp[rows, :rr] = x[rows].float() @ a_stack[s, :rr].float().t()
+    return tmp
+
+
+def lora_expand_add(
+    y: torch.Tensor,        # [T, >= out_offset + N], modified in place
+    tmp: torch.Tensor,      # [T, R] fp32
+    b_stack: torch.Tensor,  # [S, N, R]
+    scale: torch.Tensor,    # [S] fp32
+    ranks: torch.Tensor,    # [S] int32
+    slot_idx: torch.Tensor,  # [T] int32
+    out_offset: int = 0,
+) -> torch.Tensor:
+    """Batched multi-LoRA expand, fp32 reference: per row t,
+    y[t, off:off+N] = (y + scale[slot_t] * tmp[t, :rr] @ b_stack[slot_t, :, :rr]^T)
+    rounded once to y's dtype. Skipped rows and the columns outside
+    [off, off+N) keep their bits."""
+    N, R = b_stack.shape[1], b_stack.shape[2]
+    if out_offset < 0 or out_offset + N > y.shape[1]:
+        raise ValueError("out_offset + N exceeds the row of y")
+    for s, rr, rows in _lora_rows_by_slot(slot_idx, ranks, R):
+        d = tmp[rows, :rr].float() @ b_stack[s, :, :rr].float().t()
+        cur = y[rows, out_offset:out_offset + N].float()
+        y[rows, out_offset:out_offset + N] = (
+            cur + float(scale[s]) * d
+        ).to(y.dtype)
+    return y
