@@ -32,6 +32,7 @@ KERNEL_SOURCES = [
     "sampling.hip",
     "skinny_gemm.hip",
     "w8_gemm.hip",
+    "w4_gemm.hip",
     "lora.hip",
     "gemm8.hip",
     "mfma_probe.hip",

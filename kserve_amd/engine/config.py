@@ -54,17 +54,18 @@ class ModelConfig:
     # absolute-position bound since round 2.
     sliding_window: int = None
     # weight-only quantization of the attention/MLP projections: None
-    # (bf16) or "fp8" (OCP E4M3 codes + per-channel f32 scales, W8A16;
-    # kserve_amd/ops/quant.py). lm_head and the embedding stay bf16.
+    # (bf16), "fp8" (OCP E4M3 codes + per-channel f32 scales, W8A16) or
+    # "mxfp4" (OCP E2M1 codes + one E8M0 scale per 32 inputs, W4A16);
+    # kserve_amd/ops/quant.py. lm_head and the embedding stay bf16.
     quantization: Optional[str] = None
 
     def __post_init__(self):
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_heads
-        if self.quantization not in (None, "fp8"):
+        if self.quantization not in (None, "fp8", "mxfp4"):
             raise ValueError(
                 f"unknown quantization {self.quantization!r}; "
-                "supported: None, 'fp8'"
+                "supported: None, 'fp8', 'mxfp4'"
             )
 
     @property
@@ -151,10 +152,13 @@ class ModelConfig:
         """Parse a HuggingFace config.json (model dir contract /mnt/models)."""
         with open(config_path) as f:
             cfg = json.load(f)
-        # pre-quantized checkpoint (weight-only fp8 is how it is served:
-        # any activation scales it carries are ignored)
+        # pre-quantized checkpoint (weight-only is how it is served: any
+        # activation scales it carries are ignored). Only the quant_method
+        # string is read; the tensors themselves are recognised by dtype
+        # and shape at load (LlamaForCausalLM.load_hf_state_dict).
         qcfg = cfg.get("quantization_config") or {}
-        quantization = "fp8" if qcfg.get("quant_method") == "fp8" else None
+        method = qcfg.get("quant_method")
+        quantization = method if method in ("fp8", "mxfp4") else None
         return cls(
             quantization=quantization,
             vocab_size=cfg["vocab_size"],

@@ -356,12 +356,13 @@ class LlamaForCausalLM(nn.Module):
         self.config = config
         if config.quantization is not None and config.num_local_experts > 0:
             # the experts are stacked bmm weights and would need a grouped
-            # fp8 kernel; quantizing only the attention projections (~5 %
-            # of the bytes) silently would be worse than refusing
+            # quantized kernel; quantizing only the attention projections
+            # (~5 % of the bytes) silently would be worse than refusing
             raise ValueError(
                 f"quantization={config.quantization!r} does not support "
                 "mixture-of-experts models (num_local_experts > 0): the "
-                "stacked expert weights have no fp8 kernel"
+                "stacked expert weights have no quantized (fp8 or mxfp4) "
+                "kernel"
             )
         dtype = dtype or (
             torch.bfloat16 if config.dtype == "bfloat16" else torch.float32
@@ -494,10 +495,13 @@ class LlamaForCausalLM(nn.Module):
             return t() if callable(t) else t
 
         def get_w(prefix):
-            """(weight, per-channel scale or None) of one projection. A
-            projection is pre-quantized when its weight is float8_e4m3fn
-            with a sibling weight_scale (1 or out_features elements);
-            input_scale is ignored (the scheme is weight-only)."""
+            """(weight, scale or None) of one projection. A projection is
+            pre-quantized fp8 when its weight is float8_e4m3fn with a
+            sibling weight_scale (1 or out_features elements), and
+            pre-quantized MXFP4 when its weight is uint8 [M, K/2] with a
+            sibling uint8 / float8_e8m0fnu weight_scale [M, K/32] (checked:
+            shape, no code 255). input_scale is ignored (the schemes are
+            weight-only)."""
             if (prefix + ".weight_scale_inv") in tensors:
                 raise ValueError(
                     f"{prefix}.weight_scale_inv: block-wise fp8 scales are "
@@ -505,6 +509,16 @@ class LlamaForCausalLM(nn.Module):
                     "only)"
                 )
             w = get(prefix + ".weight")
+            if w.dtype == torch.uint8:
+                if w.dim() != 2 or (prefix + ".weight_scale") not in tensors:
+                    raise ValueError(
+                        f"{prefix}.weight is uint8 (packed mxfp4 codes) but "
+                        f"{prefix}.weight_scale is missing"
+                    )
+                return w, quant.check_mxfp4_scale(
+                    get(prefix + ".weight_scale"), w.shape[0],
+                    w.shape[1] * 2, name=prefix + ".weight_scale",
+                )
             if w.dtype != quant.FP8_DTYPE:
                 return w, None
             if (prefix + ".weight_scale") not in tensors:

@@ -299,7 +299,7 @@ def _w8_scratch(device, out_features: int, in_features: int) -> torch.Tensor:
     if buf is None or buf.numel() < w8_scratch_numel(out_features, in_features):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(
-                "fp8 dequant scratch too small during graph capture; "
+                "dequant scratch too small during graph capture; "
                 "call ops.reserve_w8_scratch when the weight is quantized"
             )
         reserve_w8_scratch(device, out_features, in_features)
@@ -350,6 +350,66 @@ def linear_w8(
         r1 = min(M, r0 + rows)
         w = buf[: (r1 - r0) * K].view(r1 - r0, K)
         C.dequant_fp8_rows(w, qweight[r0:r1], scale[r0:r1])
+        parts.append(
+            F.linear(x, w, None if bias is None else bias[r0:r1])
+        )
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+
+
+# Largest token batch ops.linear_w4 sends to the MXFP4-weight skinny GEMM;
+# above it the weight is dequantized into the shared scratch and hipBLASLt
+# runs the GEMM. Measured at N = 1/16/64/128 on the four Llama-3-8B
+# projection shapes, the kernel beat dequant + hipBLASLt in every cell
+# (1.8-5.2x), so 128, the largest measured N and the kernel's own limit
+# (its X tile fills 64 KB of LDS there), is the value (A/B table:
+# profiles/w4_gemm.md, tools/gemm_bench.py --w4).
+W4_MAX_TOKENS = 128
+
+
+def linear_w4(
+    x: torch.Tensor,
+    qweight: torch.Tensor,
+    weight_scale: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Weight-only MXFP4 linear: x @ dequant(qweight, weight_scale)^T (+ bias).
+
+    qweight uint8 [M, K/2], weight_scale uint8 [M, K/32]
+    (kserve_amd.ops.quant). GPU: decode-sized batches run the fp4-weight
+    MFMA skinny GEMM (weights cross HBM once, as 4.25 bits each);
+    everything else (prefill, large batches, odd shapes) dequantizes into
+    the scratch shared with linear_w8 and runs hipBLASLt.
+    """
+    if not x.is_cuda:
+        return torch_ref.linear_w4(x, qweight, weight_scale, bias)
+    C = _native("linear_w4")
+    import torch.nn.functional as F
+
+    M, K = qweight.shape[0], qweight.shape[1] * 2
+    if (
+        x.dim() == 2
+        and 0 < x.shape[0] <= W4_MAX_TOKENS
+        and M % 64 == 0
+        and K % 128 == 0
+        and x.dtype == torch.bfloat16
+        and x.stride(1) == 1
+        and x.stride(0) % 8 == 0
+        and x.data_ptr() % 16 == 0
+    ):
+        out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
+        C.skinny_gemm_w4(out, x, qweight, weight_scale)
+        if bias is not None:
+            out += bias
+        return out
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"linear_w4 on GPU needs bf16 activations, got {x.dtype}")
+    buf = _w8_scratch(x.device, M, K)
+    rows = min(M, buf.numel() // K)
+    parts = []
+    for r0 in range(0, M, rows):
+        r1 = min(M, r0 + rows)
+        w = buf[: (r1 - r0) * K].view(r1 - r0, K)
+        C.dequant_mxfp4_rows(w, qweight[r0:r1], weight_scale[r0:r1])
         parts.append(
             F.linear(x, w, None if bias is None else bias[r0:r1])
         )

@@ -60,6 +60,11 @@ hipError_t ks_gemm8(void*, const void*, const void*, int, int, int, int,
 int ks_skinny_gemm_w8_nsplit(int, int);
 hipError_t ks_skinny_gemm_w8(void*, void*, const void*, const void*,
                              const void*, int, int, int, long, hipStream_t);
+int ks_skinny_gemm_w4_nsplit(int, int);
+hipError_t ks_skinny_gemm_w4(void*, void*, const void*, const void*,
+                             const void*, int, int, int, long, hipStream_t);
+hipError_t ks_dequant_mxfp4_rows(void*, const void*, const void*, long, int,
+                                 hipStream_t);
 hipError_t ks_dequant_fp8_rows(void*, const void*, const void*, long, int,
                                hipStream_t);
 hipError_t ks_lora_shrink(void*, const void*, const void*, const void*,
@@ -469,6 +474,66 @@ void dequant_fp8_rows(at::Tensor& out, at::Tensor& qweight,
             "dequant_fp8_rows");
 }
 
+// qweight uint8 [M, K/2] (two E2M1 codes per byte), scale uint8 [M, K/32]
+// (E8M0), both contiguous; 16-byte aligned codes for the dwordx4 loads
+#define CHECK_MXFP4_WEIGHT(q, scale)                                       \
+  TORCH_CHECK((q).scalar_type() == at::kByte && (q).is_cuda() &&           \
+                  (q).dim() == 2 && (q).is_contiguous() &&                 \
+                  (q).size(1) % 16 == 0 &&                                 \
+                  ((uintptr_t)(q).data_ptr() & 15) == 0,                   \
+              #q " must be a contiguous, 16-byte aligned 2-D uint8 GPU "   \
+                 "tensor [out, in/2] with in % 32 == 0");                  \
+  TORCH_CHECK((scale).scalar_type() == at::kByte && (scale).is_cuda() &&   \
+                  (scale).dim() == 2 && (scale).is_contiguous() &&         \
+                  (scale).size(0) == (q).size(0) &&                        \
+                  (scale).size(1) * 16 == (q).size(1),                     \
+              #scale " must be uint8 [out, in/32] on GPU")
+
+void skinny_gemm_w4(at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
+                    at::Tensor& scale) {
+  // out [N, M] bf16 = x [N, K] bf16 @ dequant(qweight [M, K/2], scale)^T
+  CHECK_BF16_CONTIG(out);
+  CHECK_MXFP4_WEIGHT(qweight, scale);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_cuda() &&
+                  x.dim() == 2 && x.stride(1) == 1,
+              "x must be bf16 row-dense");
+  int N = x.size(0);
+  int K = x.size(1);
+  int M = qweight.size(0);
+  TORCH_CHECK(qweight.size(1) * 2 == K && out.dim() == 2 &&
+                  out.size(0) == N && out.size(1) == M,
+              "shape mismatch");
+  TORCH_CHECK(N >= 1 && N <= 128 && M % 64 == 0 && K % 128 == 0,
+              "skinny_gemm_w4 needs 1 <= N <= 128, M % 64 == 0, K % 128 == 0");
+  at::Tensor ws;
+  void* wsp = nullptr;
+  const int nsplit = ks_skinny_gemm_w4_nsplit(M, K);
+  if (nsplit > 1) {
+    // bf16 partials (each a full-precision-accumulated K/nsplit dot)
+    ws = at::empty({(long)nsplit * N * M},
+                   at::TensorOptions().dtype(at::kBFloat16).device(x.device()));
+    wsp = ws.data_ptr();
+  }
+  check_hip(ks_skinny_gemm_w4(out.data_ptr(), wsp, x.data_ptr(),
+                              qweight.data_ptr(), scale.data_ptr(), M, K, N,
+                              (long)x.stride(0), current_stream()),
+            "skinny_gemm_w4");
+}
+
+void dequant_mxfp4_rows(at::Tensor& out, at::Tensor& qweight,
+                        at::Tensor& scale) {
+  // out [M, K] bf16 = e2m1(qweight [M, K/2]) * 2^(scale [M, K/32] - 127)
+  CHECK_BF16_CONTIG(out);
+  CHECK_MXFP4_WEIGHT(qweight, scale);
+  TORCH_CHECK(out.numel() == qweight.numel() * 2, "shape mismatch");
+  TORCH_CHECK(((uintptr_t)out.data_ptr() & 15) == 0,
+              "out must be 16-byte aligned");
+  check_hip(ks_dequant_mxfp4_rows(out.data_ptr(), qweight.data_ptr(),
+                                  scale.data_ptr(), (long)qweight.size(0),
+                                  (int)qweight.size(1) * 2, current_stream()),
+            "dequant_mxfp4_rows");
+}
+
 // [T, cols] bf16 rows of a possibly wider buffer: unit inner stride, every
 // row start 16-byte aligned (the LoRA kernels use 16 B / 8 B vectors)
 #define CHECK_LORA_ROWS(t)                                                 \
@@ -605,6 +670,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "decode GEMM, fp8 e4m3 weights x bf16 activations (N<=256)");
   m.def("dequant_fp8_rows", &dequant_fp8_rows,
         "fp8 e4m3 rows * per-row scale -> bf16");
+  m.def("skinny_gemm_w4", &skinny_gemm_w4,
+        "decode GEMM, MXFP4 weights x bf16 activations (N<=128)");
+  m.def("dequant_mxfp4_rows", &dequant_mxfp4_rows,
+        "MXFP4 rows (e2m1 codes, e8m0 block scales) -> bf16");
   m.def("lora_shrink", &lora_shrink,
         "batched multi-LoRA shrink: tmp = x . A[slot]^T per row (f32 out)");
   m.def("lora_expand_add", &lora_expand_add,

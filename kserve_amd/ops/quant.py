@@ -1,14 +1,30 @@
-"""Weight-only fp8 quantization (W8A16): format and host-side quantizer.
+"""Weight-only quantization (fp8 W8A16, MXFP4 W4A16): formats and
+host-side quantizers.
 
-Format: OCP ``float8_e4m3fn`` codes (never ``fnuz``) with one fp32 scale per
+fp8 format: OCP ``float8_e4m3fn`` codes (never ``fnuz``) with one fp32 scale per
 output channel (weight row); ``w ~= float(q) * scale[row]``. Activations
 stay bf16, so the only approximation is this one-time rounding of the
 weights: the fp8 -> bf16 convert in the kernel is exact (E4M3 fits bf16's
 mantissa) and the scale multiplies the fp32 accumulator after the K
 reduction (``torch_ref.linear_w8`` / ``w8_gemm.hip``).
 
-The quantizer is plain torch: it runs once at load, on whatever device the
-shard is on.
+MXFP4 format (OCP microscaling), for a weight ``w [M, K]``, ``K % 32 == 0``:
+
+- ``qweight``: ``uint8 [M, K/2]``. Element ``2i`` of a row is in bits 3:0 of
+  byte ``i``; element ``2i+1`` is in bits 7:4.
+- A 4-bit code is sign (bit 3) plus a 3-bit magnitude index into
+  ``{0, 0.5, 1, 1.5, 2, 3, 4, 6}`` (E2M1; no Inf, no NaN).
+- ``weight_scale``: ``uint8 [M, K/32]``, E8M0: code ``c`` means
+  ``2^(c-127)``; code 255 (NaN) is invalid and refused at load.
+- ``w[m][k] ~= e2m1(code[m][k]) * 2^(weight_scale[m][k/32] - 127)``.
+
+The scale is a power of two, so applying it (in the kernel's convert,
+``w4_gemm.hip``, or in ``torch_ref.linear_w4``) is exact wherever the
+product is a normal bf16; as with fp8 the only approximation is the
+one-time rounding of the weights.
+
+The quantizers are plain torch: they run once at load, on whatever device
+the shard is on.
 """
 
 from __future__ import annotations
@@ -20,14 +36,14 @@ import torch
 FP8_DTYPE = torch.float8_e4m3fn
 FP8_MAX = 448.0  # largest finite e4m3fn magnitude
 
-QUANTIZATION_METHODS = (None, "fp8")
+QUANTIZATION_METHODS = (None, "fp8", "mxfp4")
 
 
 def check_quantization(name: Optional[str]) -> Optional[str]:
     """Validate a quantization method name (config time)."""
     if name not in QUANTIZATION_METHODS:
         raise ValueError(
-            f"unknown quantization {name!r}; supported: None, 'fp8'"
+            f"unknown quantization {name!r}; supported: None, 'fp8', 'mxfp4'"
         )
     return name
 
@@ -65,3 +81,92 @@ def expand_scale(scale: torch.Tensor, out_features: int) -> torch.Tensor:
             f"{out_features} (block-wise scales are not supported)"
         )
     return s.contiguous()
+
+
+# ---------------------------------------------------------------- MXFP4 --
+
+MXFP4_BLOCK = 32
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+E2M1_MAX = 6.0
+E8M0_BIAS = 127
+E8M0_NAN = 255
+
+
+def quantize_mxfp4(w: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """w [M, K] (bf16/f32), K % 32 == 0 -> (qweight uint8 [M, K/2],
+    weight_scale uint8 [M, K/32]).
+
+    Per block of 32: e = floor(log2(amax)) - 2 clamped to [-126, 127] (so
+    amax / 2^e is in [4, 8): the top binade of E2M1, saturating above 6);
+    an all-zero block gets scale code 127. Elements are w / 2^e clamped to
+    [-6, 6] and rounded to the nearest E2M1 value, ties to the even
+    mantissa. A value that rounds to zero gets code 0x0, never 0x8, which
+    makes quantizing a dequantized weight the identity.
+    """
+    assert w.dim() == 2, "quantize_mxfp4 expects [out, in]"
+    M, K = w.shape
+    if K % MXFP4_BLOCK != 0:
+        raise ValueError(
+            f"mxfp4 needs in_features % {MXFP4_BLOCK} == 0, got {K}"
+        )
+    wf = w.float().reshape(M, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2).clamp(max=torch.finfo(torch.float32).max)
+    # frexp: amax = m * 2^ex with m in [0.5, 1), so floor(log2) = ex - 1
+    _, ex = torch.frexp(amax)
+    e = (ex.to(torch.int32) - 3).clamp(-126, 127)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    # ldexp by -e in two exact halves: 2^126 * 6 would overflow in one
+    h = torch.div(e, 2, rounding_mode="floor")
+    v = torch.ldexp(torch.ldexp(wf, -h[..., None]), -(e - h)[..., None])
+    a = v.abs().clamp(max=E2M1_MAX)
+    # thresholds are the midpoints; >= where the tie goes up to an even code
+    idx = (
+        (a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8)
+        + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8)
+        + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8)
+        + (a > 5.0).to(torch.uint8)
+    )
+    sign = ((v < 0) & (idx > 0)).to(torch.uint8) << 3
+    codes = (idx | sign).reshape(M, K // 2, 2)
+    qweight = codes[..., 0] | (codes[..., 1] << 4)
+    scale = (e + E8M0_BIAS).to(torch.uint8)
+    return qweight.contiguous(), scale.contiguous()
+
+
+def dequantize_mxfp4(qweight: torch.Tensor, weight_scale: torch.Tensor,
+                     dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Table lookup times 2^(scale - 127), rounded once to ``dtype``."""
+    M, K2 = qweight.shape
+    lut = torch.tensor(
+        E2M1_VALUES + tuple(-x for x in E2M1_VALUES),
+        dtype=torch.float32, device=qweight.device,
+    )
+    q = qweight.to(torch.int64)
+    vals = lut[torch.stack((q & 0xF, q >> 4), dim=-1)]  # [M, K/2, 2]
+    vals = vals.reshape(M, K2 * 2 // MXFP4_BLOCK, MXFP4_BLOCK)
+    ex = weight_scale.to(torch.int32) - E8M0_BIAS
+    return torch.ldexp(vals, ex[..., None]).reshape(M, K2 * 2).to(dtype)
+
+
+def check_mxfp4_scale(scale: torch.Tensor, out_features: int,
+                      in_features: int, name: str = "weight_scale"
+                      ) -> torch.Tensor:
+    """Checkpoint E8M0 scale (uint8 or float8_e8m0fnu) -> uint8
+    [out_features, in_features / 32]; refuses a wrong shape and code 255."""
+    if scale.dtype != torch.uint8:
+        e8m0 = getattr(torch, "float8_e8m0fnu", None)
+        if e8m0 is None or scale.dtype != e8m0:
+            raise ValueError(
+                f"{name}: mxfp4 scales must be uint8 or float8_e8m0fnu, "
+                f"got {scale.dtype}"
+            )
+        scale = scale.view(torch.uint8)
+    want = (out_features, in_features // MXFP4_BLOCK)
+    if in_features % MXFP4_BLOCK != 0 or tuple(scale.shape) != want:
+        raise ValueError(
+            f"{name} has shape {tuple(scale.shape)}, expected {want} "
+            f"(one E8M0 scale per {MXFP4_BLOCK} input features)"
+        )
+    if bool((scale == E8M0_NAN).any()):
+        raise ValueError(f"{name} holds the E8M0 NaN code 255")
+    return scale

@@ -327,6 +327,25 @@ def linear_w8(
     return y.to(x.dtype)
 
 
+def linear_w4(
+    x: torch.Tensor,
+    qweight: torch.Tensor,
+    weight_scale: torch.Tensor,
+    bias: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Weight-only MXFP4 linear, fp32 reference: x [.., K] @ w^T with
+    w = dequantize_mxfp4(qweight [M, K/2], weight_scale [M, K/32]) exact in
+    fp32 (a 3-bit magnitude times a power of two). One plain matmul over
+    the whole K, whatever order the HIP kernel walks it in."""
+    from kserve_amd.ops import quant
+
+    w = quant.dequantize_mxfp4(qweight, weight_scale, torch.float32)
+    y = x.float() @ w.t()
+    if bias is not None:
+        y = y + bias.float()
+    return y.to(x.dtype)
+
+
 def _lora_rows_by_slot(slot_idx: torch.Tensor, ranks: torch.Tensor, R: int):
     """Yield (slot, rr, rows) for every slot in [0, S) some row references;
     rows with a slot outside that range are skipped, as in the kernels."""

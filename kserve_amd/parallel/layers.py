@@ -32,6 +32,9 @@ class _QuantLinearBase(nn.Module):
     quantization="fp8": ``qweight`` (float8_e4m3fn) + ``weight_scale``
     (f32 [out_local]) INSTEAD of ``weight`` — the layer never holds both
     copies (kserve_amd.ops.quant has the format).
+    quantization="mxfp4": ``qweight`` (uint8 [out_local, in_local/2], two
+    E2M1 codes per byte) + ``weight_scale`` (uint8 [out_local,
+    in_local/32], E8M0), again instead of ``weight``.
     """
 
     def _alloc_weight(
@@ -46,6 +49,23 @@ class _QuantLinearBase(nn.Module):
             )
             self.weight_scale = nn.Parameter(
                 torch.empty(out_local, dtype=torch.float32),
+                requires_grad=False,
+            )
+        elif self.quantization == "mxfp4":
+            if in_local % quant.MXFP4_BLOCK != 0:
+                raise ValueError(
+                    f"mxfp4 needs the per-rank in_features ({in_local}) to "
+                    f"be a multiple of {quant.MXFP4_BLOCK}"
+                )
+            self.qweight = nn.Parameter(
+                torch.empty(out_local, in_local // 2, dtype=torch.uint8),
+                requires_grad=False,
+            )
+            self.weight_scale = nn.Parameter(
+                torch.empty(
+                    out_local, in_local // quant.MXFP4_BLOCK,
+                    dtype=torch.uint8,
+                ),
                 requires_grad=False,
             )
         else:
@@ -64,7 +84,28 @@ class _QuantLinearBase(nn.Module):
             if scale is None:
                 raise ValueError("fp8 checkpoint weight without weight_scale")
             return w.to(dev), scale.float().to(dev)
+        if w.dtype == torch.uint8:
+            raise ValueError(
+                "an mxfp4 checkpoint cannot be loaded with quantization='fp8'"
+            )
         return quant.quantize_fp8_per_channel(w.to(dev))
+
+    def _to_mxfp4(self, w: torch.Tensor, scale: Optional[torch.Tensor]):
+        """One already-sliced shard -> (packed codes, E8M0 block scales) on
+        the layer's device. ``scale`` is the matching [rows, in/32] slice of
+        a pre-quantized checkpoint (None for a bf16/f32 shard, which is
+        quantized here, after slicing)."""
+        dev = self.qweight.device
+        if w.dtype == torch.uint8:
+            if scale is None:
+                raise ValueError("mxfp4 checkpoint weight without weight_scale")
+            scale = quant.check_mxfp4_scale(scale, w.shape[0], w.shape[1] * 2)
+            return w.to(dev), scale.to(dev)
+        if w.dtype == quant.FP8_DTYPE:
+            raise ValueError(
+                "an fp8 checkpoint cannot be loaded with quantization='mxfp4'"
+            )
+        return quant.quantize_mxfp4(w.to(dev))
 
     def _store_weight(self, pieces, scales=None) -> None:
         """Store this rank's shard, given as row-blocks that are
@@ -76,21 +117,43 @@ class _QuantLinearBase(nn.Module):
             self.weight_scale.data.copy_(torch.cat([s for _, s in qs], dim=0))
             ops.reserve_w8_scratch(self.qweight.device, *self.qweight.shape)
             return
+        if self.quantization == "mxfp4":
+            qs = [self._to_mxfp4(w, s) for w, s in zip(pieces, scales)]
+            self.qweight.data.copy_(torch.cat([q for q, _ in qs], dim=0))
+            self.weight_scale.data.copy_(torch.cat([s for _, s in qs], dim=0))
+            # the scratch is shared with fp8 and sized in bf16 elements
+            ops.reserve_w8_scratch(
+                self.qweight.device, self.qweight.shape[0],
+                self.qweight.shape[1] * 2,
+            )
+            return
         dt = self.weight.dtype
-        ws = [
-            quant.dequantize_fp8(w, s, dt) if w.dtype == quant.FP8_DTYPE
-            else w.to(dt)
-            for w, s in zip(pieces, scales)
-        ]
+
+        def to_dt(w, s):
+            if w.dtype == quant.FP8_DTYPE:
+                return quant.dequantize_fp8(w, s, dt)
+            if w.dtype == torch.uint8:
+                if s is None:
+                    raise ValueError(
+                        "mxfp4 checkpoint weight without weight_scale"
+                    )
+                s = quant.check_mxfp4_scale(s, w.shape[0], w.shape[1] * 2)
+                return quant.dequantize_mxfp4(w, s, dt)
+            return w.to(dt)
+
+        ws = [to_dt(w, s) for w, s in zip(pieces, scales)]
         self.weight.data.copy_(torch.cat(ws, dim=0))
 
     @torch.no_grad()
     def random_init_weight(self, std: float, generator) -> None:
-        """normal_ does not exist for fp8: draw a temporary in bf16 on the
-        layer's device and quantize it."""
-        if self.quantization == "fp8":
+        """normal_ does not exist for fp8 or packed fp4 codes: draw a
+        temporary in bf16 on the layer's device and quantize it."""
+        if self.quantization is not None:
+            shape = tuple(self.qweight.shape)
+            if self.quantization == "mxfp4":
+                shape = (shape[0], shape[1] * 2)
             tmp = torch.empty(
-                self.qweight.shape, dtype=torch.bfloat16,
+                shape, dtype=torch.bfloat16,
                 device=self.qweight.device,
             ).normal_(0.0, std, generator=generator)
             self._store_weight([tmp])
@@ -100,6 +163,8 @@ class _QuantLinearBase(nn.Module):
     def _linear(self, x: torch.Tensor, bias: Optional[torch.Tensor] = None):
         if self.quantization == "fp8":
             return ops.linear_w8(x, self.qweight, self.weight_scale, bias)
+        if self.quantization == "mxfp4":
+            return ops.linear_w4(x, self.qweight, self.weight_scale, bias)
         return ops.linear(x, self.weight, bias)
 
 
@@ -299,6 +364,10 @@ class RowParallelLinear(_QuantLinearBase):
                     yc = ops.linear_w8(
                         x, self.qweight[rows], self.weight_scale[rows]
                     )
+                elif self.quantization == "mxfp4":
+                    yc = ops.linear_w4(
+                        x, self.qweight[rows], self.weight_scale[rows]
+                    )
                 else:
                     yc = ops.linear(x, self.weight[rows])
                 works.append(comm.tp_all_reduce_async(yc))
@@ -330,10 +399,30 @@ class RowParallelLinear(_QuantLinearBase):
         """Slice this rank's input features, then quantize: every rank gets
         its own per-channel scales, so its partial is correctly scaled
         before the all-reduce. A pre-quantized checkpoint's per-channel
-        scale applies to every column slice unchanged."""
+        scale applies to every column slice unchanged. A pre-quantized
+        MXFP4 weight is sliced as bytes (two features each) with the
+        matching scale columns (32 features each)."""
         r = comm.get_state().tp_rank
         lo, hi = r * self.in_per_rank, (r + 1) * self.in_per_rank
-        self._store_weight([full_weight[:, lo:hi]], [weight_scale])
+        if full_weight.dtype == torch.uint8:
+            if self.in_per_rank % quant.MXFP4_BLOCK != 0:
+                raise ValueError(
+                    f"mxfp4 row-parallel shard: per-rank in_features "
+                    f"({self.in_per_rank}) must be a multiple of "
+                    f"{quant.MXFP4_BLOCK} so that no scale block is split"
+                )
+            if weight_scale is None:
+                raise ValueError("mxfp4 checkpoint weight without weight_scale")
+            weight_scale = quant.check_mxfp4_scale(
+                weight_scale, full_weight.shape[0], full_weight.shape[1] * 2
+            )
+            b = quant.MXFP4_BLOCK
+            self._store_weight(
+                [full_weight[:, lo // 2:hi // 2]],
+                [weight_scale[:, lo // b:hi // b]],
+            )
+        else:
+            self._store_weight([full_weight[:, lo:hi]], [weight_scale])
         if self.bias is not None and full_bias is not None:
             self.bias.data.copy_(full_bias.to(self.bias.dtype))
 

@@ -60,7 +60,7 @@ def engine_model_config(args):
     )
     if getattr(args, "expert_parallel", False):
         model_cfg.expert_parallel = True
-    # --quantization fp8: a bf16 checkpoint is quantized at load; a
+    # --quantization fp8|mxfp4: a bf16 checkpoint is quantized at load; a
     # pre-quantized one already set it from its quantization_config
     quantization = getattr(args, "quantization", None)
     if quantization not in (None, "none"):
@@ -177,9 +177,9 @@ def build_parser():
     parser.add_argument("--kv-offload-bytes", dest="kv_offload_bytes", type=int, default=0)
     parser.add_argument("--kv-cache-dtype", dest="kv_cache_dtype", default="auto",
                         choices=["auto", "fp8"])
-    # weight-only fp8 (E4M3) for the attention/MLP projections
+    # weight-only fp8 (E4M3) or MXFP4 for the attention/MLP projections
     parser.add_argument("--quantization", dest="quantization", default=None,
-                        choices=["none", "fp8"])
+                        choices=["none", "fp8", "mxfp4"])
     # LoRA adapter serving (reference: --enable-lora --lora-modules name=path)
     parser.add_argument("--speculative-draft-model",
                         dest="speculative_draft_model", default=None,

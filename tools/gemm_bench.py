@@ -4,12 +4,17 @@ shape, to judge hipBLASLt (tuned/untuned) against the HBM roofline.
 
 Run on GPU: python tools/gemm_bench.py [--tune]
             python tools/gemm_bench.py --w8 [--out FILE.md]
+            python tools/gemm_bench.py --w4 [--out FILE.md]
 
 --w8 is the A/B behind ops.W8_MAX_TOKENS (profiles/w8_gemm.md): per
 Llama-3-8B projection shape and token batch it times, in one process and
 interleaved, (a) ops.linear on bf16 weights, (b) the fp8-weight skinny GEMM
 and (c) dequant + hipBLASLt, the path ops.linear_w8 takes above the
 threshold.
+
+--w4 is the same A/B behind ops.W4_MAX_TOKENS (profiles/w4_gemm.md), with
+the columns (a) ops.linear on bf16 weights, (b) the fp8-weight skinny GEMM,
+(c) the MXFP4-weight skinny GEMM and (d) MXFP4 dequant + hipBLASLt.
 """
 
 import argparse
@@ -23,8 +28,10 @@ parser.add_argument("--tune", action="store_true")
 parser.add_argument("--iters", type=int, default=50)
 parser.add_argument("--w8", action="store_true",
                     help="fp8-weight A/B table instead of the bf16 table")
+parser.add_argument("--w4", action="store_true",
+                    help="MXFP4-weight A/B table instead of the bf16 table")
 parser.add_argument("--out", default=None,
-                    help="--w8: also write the table as markdown here")
+                    help="--w8/--w4: also write the table as markdown here")
 args = parser.parse_args()
 
 if args.tune:
@@ -165,8 +172,125 @@ def bench_w8():
             f.write("\n".join(lines) + "\n" + tail + "\n")
 
 
+def bench_w4():
+    """bench_w8's method (interleaved rounds, a weight set larger than the
+    256 MB Infinity Cache even at 4.25 bits per weight) with the MXFP4
+    kernel and its dequant path beside the bf16 and fp8 kernels. TB/s is
+    weight bytes of the variant's own format (scales included) over its
+    time."""
+    import statistics
+
+    from kserve_amd import ops
+    from kserve_amd.ops.quant import quantize_fp8_per_channel, quantize_mxfp4
+
+    shapes = [  # (name, K in, M out): Llama-3-8B projections
+        ("qkv", 4096, 6144),
+        ("o", 4096, 4096),
+        ("gate_up", 4096, 28672),
+        ("down", 14336, 4096),
+    ]
+    batches = [1, 16, 64, 128]
+    rounds = 5
+    for _, K, M in shapes:
+        ops.reserve_w8_scratch(dev, M, K)
+
+    def timed(fn, copies, iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for i in range(iters):
+            fn(i % copies)
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / iters * 1000
+
+    lines = [
+        "| shape | K | M | N | (a) bf16 us | (a) TB/s | (b) w8 us | (b) TB/s "
+        "| (c) w4 us | (c) TB/s | (d) dequant+GEMM us | (c)/(b) | (c)/(a) "
+        "| (c)<=(d) |",
+        "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|",
+    ]
+    print(lines[0]); print(lines[1])
+    worst = {n: True for n in batches}
+    for name, K, M in shapes:
+        copies = max(2, -(-(768 << 20) // (M * K)))
+        gen = torch.Generator(device=dev).manual_seed(0)
+        ws, q8, s8, q4, s4 = [], [], [], [], []
+        for _ in range(copies):
+            w = torch.randn(M, K, dtype=torch.bfloat16, device=dev,
+                            generator=gen) * 0.02
+            q, s = quantize_fp8_per_channel(w)
+            ws.append(w); q8.append(q); s8.append(s)
+            q, s = quantize_mxfp4(w)
+            q4.append(q); s4.append(s)
+        torch.cuda.empty_cache()
+        for N in batches:
+            x = torch.randn(N, K, dtype=torch.bfloat16, device=dev,
+                            generator=gen) / 8
+            out = torch.empty(N, M, dtype=torch.bfloat16, device=dev)
+
+            def fa(i):
+                return ops.linear(x, ws[i])
+
+            def fb(i):
+                kserve_amd_C.skinny_gemm_w8(out, x, q8[i], s8[i])
+
+            def fc(i):
+                kserve_amd_C.skinny_gemm_w4(out, x, q4[i], s4[i])
+
+            def fd(i):
+                return ops.linear_w4(x, q4[i], s4[i])
+
+            iters = max(args.iters, 2 * copies)
+            res = {"a": [], "b": [], "c": [], "d": []}
+            keep = ops.W4_MAX_TOKENS
+            try:
+                for r in range(rounds + 1):  # round 0 is warm-up
+                    for key, fn in (("a", fa), ("b", fb), ("c", fc), ("d", fd)):
+                        ops.W4_MAX_TOKENS = 0 if key == "d" else keep
+                        t = timed(fn, copies, iters)
+                        if r:
+                            res[key].append(t)
+            finally:
+                ops.W4_MAX_TOKENS = keep
+            a, b, c, d = (statistics.median(res[k]) for k in "abcd")
+            spread = max(
+                (max(res[k]) - min(res[k])) / statistics.median(res[k])
+                for k in "abcd"
+            )
+            ok = c <= d
+            worst[N] = worst[N] and ok
+            w4_bytes = M * K // 2 + M * K // 32
+            line = (
+                f"| {name} | {K} | {M} | {N} | {a:.1f} | "
+                f"{M * K * 2 / a / 1e6:.2f} | {b:.1f} | {M * K / b / 1e6:.2f} "
+                f"| {c:.1f} | {w4_bytes / c / 1e6:.2f} | {d:.1f} "
+                f"| {c / b:.2f} | {c / a:.2f} | {'yes' if ok else 'no'} |"
+            )
+            print(line + f"  spread {spread:.0%}", flush=True)
+            lines.append(line)
+        del ws, q8, s8, q4, s4
+        torch.cuda.empty_cache()
+    # largest N such that (c) <= (d) on all four shapes and every smaller
+    # measured N (0 if none)
+    chosen = 0
+    for n in batches:
+        if not worst[n]:
+            break
+        chosen = n
+    tail = f"\nW4_MAX_TOKENS by this table: {chosen}"
+    print(tail)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n" + tail + "\n")
+
+
 if args.w8:
     bench_w8()
+    sys.exit(0)
+if args.w4:
+    bench_w4()
     sys.exit(0)
 
 

@@ -84,7 +84,7 @@ def main():
     ap.add_argument("--kv-cache-dtype", default="auto",
                     choices=["auto", "fp8"])
     ap.add_argument("--quantization", default="none",
-                    choices=["none", "fp8"])
+                    choices=["none", "fp8", "mxfp4"])
     args = ap.parse_args()
 
     import random
