@@ -27,6 +27,7 @@ KERNEL_SOURCES = [
     "activation.hip",
     "rope.hip",
     "kv_cache.hip",
+    "kv_transfer.hip",
     "attention_decode.hip",
     "attention_prefill.hip",
     "sampling.hip",

@@ -110,7 +110,7 @@ class AsyncLLMEngine:
                         item = self._submit_q.get(block=block, timeout=0.02)
                         if item is _STOP:
                             return
-                        rid, prompt, sp = item
+                        rid, prompt, sp, kv = item
                         if prompt is None:  # abort sentinel
                             self.engine.abort_request(rid)
                             # if anyone is still consuming this stream,
@@ -136,7 +136,7 @@ class AsyncLLMEngine:
                         else:
                             try:
                                 self.engine.add_request(
-                                    prompt, sp, request_id=rid
+                                    prompt, sp, request_id=rid, **kv
                                 )
                             except ValueError as e:
                                 # invalid request (e.g. over-long prompt):
@@ -177,15 +177,23 @@ class AsyncLLMEngine:
         prompt: Union[str, List[int]],
         sampling_params: Optional[SamplingParams] = None,
         request_id: Optional[str] = None,
+        kv_export: bool = False,
+        kv_import=None,
     ) -> AsyncIterator[RequestOutput]:
-        """Async stream of per-token RequestOutputs."""
+        """Async stream of per-token RequestOutputs. ``kv_export`` /
+        ``kv_import`` as in LLMEngine.add_request."""
         self._check_health()
         rid = request_id or str(uuid.uuid4())
         q: asyncio.Queue = asyncio.Queue()
         # bind the stream to the caller's loop: the engine thread publishes
         # via call_soon_threadsafe on THIS loop (server may run several)
         self._streams[rid] = (q, asyncio.get_running_loop())
-        self._submit_q.put((rid, prompt, sampling_params or SamplingParams()))
+        kv = {}
+        if kv_export or kv_import is not None:
+            kv = {"kv_export": kv_export, "kv_import": kv_import}
+        self._submit_q.put(
+            (rid, prompt, sampling_params or SamplingParams(), kv)
+        )
         try:
             while True:
                 item = await q.get()
@@ -211,15 +219,20 @@ class AsyncLLMEngine:
         if self.engine is not None:
             # abort is thread-safe enough: scheduler mutation happens in the
             # engine thread via a sentinel
-            self._submit_q.put((rid, None, None))
+            self._submit_q.put((rid, None, None, None))
 
     async def generate_full(
         self,
         prompt: Union[str, List[int]],
         sampling_params: Optional[SamplingParams] = None,
         request_id: Optional[str] = None,
+        kv_export: bool = False,
+        kv_import=None,
     ) -> RequestOutput:
         last = None
-        async for out in self.generate(prompt, sampling_params, request_id):
+        async for out in self.generate(
+            prompt, sampling_params, request_id,
+            kv_export=kv_export, kv_import=kv_import,
+        ):
             last = out
         return last

@@ -213,6 +213,19 @@ class BlockManager:
         request.num_cached_tokens = cached_tokens
         return blocks
 
+    def allocate_private(self, request: Request, num_tokens: int) -> List[int]:
+        """Allocate fresh blocks for ``num_tokens`` with no prefix-cache
+        lookup: the caller is about to overwrite every one of them (KV
+        import), so none may be shared."""
+        assert request.request_id not in self._tables, "already allocated"
+        blocks = self.take_blocks(self.blocks_needed(num_tokens))
+        self._tables[request.request_id] = blocks
+        self._seq += 1
+        self._table_seq[request.request_id] = self._seq
+        request.block_table = blocks
+        request.num_cached_tokens = 0
+        return blocks
+
     def table_seq(self, request_id: str) -> int:
         """Identity of the request's current block table (changes whenever
         the block ids are reassigned, not merely appended to)."""

@@ -204,6 +204,11 @@ class CacheConfig:
     # bytes (scale 1.0): half the KV bandwidth/capacity; attention math
     # stays fp32/bf16 after in-register conversion. GQA group <= 4, D=128.
     kv_cache_dtype: str = "auto"
+    # dtype of exported KV payloads (engine/kv_transfer.py). "auto" is the
+    # pool's own; "fp8" on a bf16 pool converts at export, byte-identical to
+    # what a kv_cache_dtype="fp8" pool stores, so it can feed one (and
+    # halves the bytes on the wire).
+    kv_export_dtype: str = "auto"
 
     def cache_torch_dtype(self, model_dtype):
         if self.kv_cache_dtype in ("fp8", "fp8_e4m3"):

@@ -16,6 +16,7 @@ import torch
 from kserve_amd import ops
 from kserve_amd.engine.config import EngineConfig
 from kserve_amd.engine.detokenizer import Detokenizer
+from kserve_amd.engine.kv_transfer import KVPayload, dtype_name
 from kserve_amd.engine.model_runner import ModelRunner
 from kserve_amd.engine.request import Request, RequestOutput, RequestStatus
 from kserve_amd.engine.sampling_params import SamplingParams
@@ -25,6 +26,10 @@ from kserve_amd.metrics import (
     LLM_E2E_HIST,
     LLM_SPEC_ACCEPTED,
     LLM_GENERATION_TOKENS,
+    LLM_KV_EXPORT_BYTES,
+    LLM_KV_EXPORTED,
+    LLM_KV_IMPORT_BYTES,
+    LLM_KV_IMPORTED,
     LLM_KV_USAGE,
     LLM_PROMPT_TOKENS,
     LLM_TTFT_HIST,
@@ -243,7 +248,13 @@ class LLMEngine:
         prompt: Union[str, List[int]],
         sampling_params: Optional[SamplingParams] = None,
         request_id: Optional[str] = None,
+        kv_export: bool = False,
+        kv_import: Optional[KVPayload] = None,
     ) -> str:
+        """Queue a request. ``kv_export``: prefill it, sample its first
+        token and finish it with reason "kv_export", its KV pages in
+        ``RequestOutput.kv_payload``. ``kv_import``: continue a request
+        another engine exported, without running its prefill."""
         request_id = request_id or str(uuid.uuid4())
         sampling_params = sampling_params or SamplingParams()
         if isinstance(prompt, str):
@@ -258,12 +269,18 @@ class LLMEngine:
                 f"prompt length {len(prompt_token_ids)} exceeds "
                 f"max_model_len {self.config.scheduler.max_model_len}"
             )
+        if kv_export or kv_import is not None:
+            self.check_kv_transfer(
+                prompt_token_ids, sampling_params, kv_export, kv_import
+            )
         req = Request(
             request_id,
             prompt_token_ids,
             sampling_params,
             eos_token_id=self.eos_token_id,
         )
+        req.kv_export = bool(kv_export)
+        req.kv_import = kv_import
         if sampling_params.lora_name:
             if self.lora_manager is None:
                 raise ValueError("no LoRA adapters registered")
@@ -290,6 +307,167 @@ class LLMEngine:
         LLM_PROMPT_TOKENS.inc(len(prompt_token_ids))
         self.scheduler.add_request(req)
         return request_id
+
+    def check_kv_transfer(
+        self, prompt_token_ids, sampling_params, kv_export, kv_import
+    ) -> None:
+        """What KV export/import refuses for now (ValueError)."""
+        if kv_export and kv_import is not None:
+            raise ValueError("a request cannot both export and import KV")
+        st = comm.get_state()
+        par = self.config.parallel
+        if max(st.tp_size, par.tensor_parallel_size) > 1 or max(
+            st.pp_size, par.pipeline_parallel_size
+        ) > 1:
+            raise ValueError(
+                "KV export/import is not supported with tensor or pipeline "
+                "parallel size above 1"
+            )
+        if sampling_params.lora_name:
+            raise ValueError("KV export/import cannot be combined with LoRA")
+        if sampling_params.guided_choice or sampling_params.response_format in (
+            "json", "json_object", "json_schema"
+        ):
+            raise ValueError(
+                "KV export/import cannot be combined with guided decoding"
+            )
+        if kv_import is not None:
+            kv_import.validate()
+            kv_import.check_compatible(
+                self.config, pool_dtype=self.runner.kv_caches[0][0].dtype
+            )
+            if list(kv_import.prompt_token_ids) != list(prompt_token_ids):
+                raise ValueError(
+                    "KV payload was computed for a different prompt"
+                )
+            if self.draft is not None:
+                # the draft model has no KV for a prompt it never saw
+                raise ValueError(
+                    "KV import cannot be combined with draft-model "
+                    "speculative decoding"
+                )
+            bm = self.scheduler.block_manager
+            need = bm.blocks_needed(kv_import.num_tokens + 1)
+            # block 0 is never handed out and the watermark stays free
+            fit = bm.num_blocks - 1 - bm.watermark_blocks
+            if need > fit:
+                # it would wait at the head of the queue forever
+                raise ValueError(
+                    f"KV payload needs {need} blocks, this engine's pool can "
+                    f"give a request {fit}"
+                )
+
+    # -- KV export / import ---------------------------------------------------
+    def _export_kv(self, req: Request, out_dtype=None) -> KVPayload:
+        """Gather the request's pages on the compute stream and start ONE
+        asynchronous copy to pinned host memory; step() waits for the
+        stream before it hands the payload out."""
+        n_tok = req.num_prompt_tokens
+        bm = self.scheduler.block_manager
+        table = bm.get_block_table(req)[: bm.blocks_needed(n_tok)]
+        out_dtype = out_dtype or self.kv_export_dtype
+        dev = ops.kv_gather_pages(
+            self.runner.kv_caches, table, n_tok, out_dtype=out_dtype
+        )
+        flat = dev.view(torch.uint8).reshape(-1)
+        if flat.is_cuda:
+            host = torch.empty(
+                flat.numel(), dtype=torch.uint8, pin_memory=True
+            )
+            host.copy_(flat, non_blocking=True)
+        else:
+            host = flat
+        m = self.config.model
+        k0 = self.runner.kv_caches[0][0]
+        LLM_KV_EXPORTED.inc()
+        LLM_KV_EXPORT_BYTES.inc(host.numel())
+        return KVPayload(
+            num_layers=len(self.runner.kv_caches),
+            num_kv_heads=k0.shape[1],
+            head_dim=k0.shape[3],
+            block_size=k0.shape[2],
+            dtype=dtype_name(dev.dtype),
+            model_name=m.model_name,
+            quantization=m.quantization,
+            prompt_token_ids=list(req.prompt_token_ids),
+            output_token_ids=list(req.output_token_ids),
+            num_tokens=n_tok,
+            data=host,
+            first_logprobs=(
+                dict(req.logprobs[0])
+                if req.sampling_params.logprobs is not None and req.logprobs
+                else None
+            ),
+        )
+
+    @property
+    def kv_export_dtype(self):
+        """Payload dtype of exports (CacheConfig.kv_export_dtype); None is
+        the pool's own."""
+        if self.config.cache.kv_export_dtype in ("fp8", "fp8_e4m3"):
+            return torch.float8_e4m3fn
+        return None
+
+    def _admit_imports(self) -> List[RequestOutput]:
+        """Admit waiting KV-import requests: copy each payload to the
+        device, scatter it into the request's fresh pages and emit the
+        carried first token. The request is then RUNNING with its prompt
+        computed, exactly as if this engine had prefilled it."""
+        outputs: List[RequestOutput] = []
+        finished: List[Request] = []
+        bm = self.scheduler.block_manager
+        for req in self.scheduler.admit_imports():
+            payload = req.kv_import
+            req.kv_import = None
+            table = bm.get_block_table(req)[: payload.num_pages]
+            src = payload.data.to(self.device, non_blocking=True)
+            ops.kv_scatter_pages(self.runner.kv_caches, table, src)
+            req.num_computed_tokens = payload.num_tokens
+            LLM_KV_IMPORTED.inc()
+            LLM_KV_IMPORT_BYTES.inc(payload.data.numel())
+            for tok in payload.output_token_ids:
+                req.append_output_token(int(tok))
+            if (
+                payload.first_logprobs is not None
+                and req.sampling_params.logprobs is not None
+            ):
+                req.logprobs.append(dict(payload.first_logprobs))
+            LLM_TTFT_HIST.observe(time.monotonic() - req.arrival_time)
+            req.maybe_finish(self.config.scheduler.max_model_len)
+            delta = self.detokenizer.decode_new(req)
+            if not req.finished and req.sampling_params.stop:
+                if self.detokenizer.check_stop_strings(req) is not None:
+                    req.status = RequestStatus.FINISHED_STOPPED
+                    req.is_finished = True
+                    req.finish_time = time.monotonic()
+            if req.finished:
+                finished.append(req)
+                LLM_E2E_HIST.observe(time.monotonic() - req.arrival_time)
+            outputs.append(
+                RequestOutput(
+                    request_id=req.request_id,
+                    new_token_ids=list(payload.output_token_ids),
+                    finished=req.finished,
+                    finish_reason=req.finish_reason,
+                    output_token_ids=(
+                        list(req.output_token_ids)
+                        if req.finished
+                        else req.output_token_ids
+                    ),
+                    num_prompt_tokens=req.num_prompt_tokens,
+                    text_delta=delta,
+                    output_text=req.output_text,
+                    logprobs=(
+                        req.logprobs
+                        if req.sampling_params.logprobs is not None
+                        else None
+                    ),
+                )
+            )
+        self.scheduler.finish_requests(finished)
+        for req in finished:
+            self.runner.release_request(req.request_id)
+        return outputs
 
     @property
     def guided_json(self):
@@ -336,6 +514,15 @@ class LLMEngine:
 
     # -- step -----------------------------------------------------------------
     def step(self) -> List[RequestOutput]:
+        if self.scheduler.num_pending_imports:
+            imported = self._admit_imports()
+            if imported:
+                if not self.scheduler.running:
+                    return imported
+                return imported + self._step()
+        return self._step()
+
+    def _step(self) -> List[RequestOutput]:
         batch = self.scheduler.schedule()
         # KV tier copies ordered before this batch's kernels
         if batch.swap_out:
@@ -507,11 +694,21 @@ class LLMEngine:
                         req.status = RequestStatus.FINISHED_STOPPED
                         req.is_finished = True
                         req.finish_time = time.monotonic()
+                kv_payload = None
+                if req.kv_export:
+                    # the decode engine applies the stop conditions to the
+                    # carried token; here the request always ends exported
+                    kv_payload = self._export_kv(req)
+                    req.status = RequestStatus.FINISHED_EXPORTED
+                    req.is_finished = True
+                    if req.finish_time is None:
+                        req.finish_time = now
                 if req.finished:
                     finished.append(req)
                     LLM_E2E_HIST.observe(now - req.arrival_time)
                 outputs.append(
                     RequestOutput(
+                        kv_payload=kv_payload,
                         request_id=req.request_id,
                         new_token_ids=(
                             []
@@ -531,6 +728,11 @@ class LLMEngine:
                         logprobs=req.logprobs if req.sampling_params.logprobs is not None else None,
                     )
                 )
+        if self.device.type == "cuda" and any(
+            o.kv_payload is not None for o in outputs
+        ):
+            # the payloads' device-to-host copies were only enqueued
+            torch.cuda.current_stream().synchronize()
         self.scheduler.finish_requests(finished)
         for req in finished:
             self.runner.release_request(req.request_id)

@@ -21,6 +21,7 @@ class RequestStatus(enum.Enum):
     FINISHED_STOPPED = enum.auto()   # hit stop token / stop string / EOS
     FINISHED_LENGTH = enum.auto()    # hit max_tokens or max_model_len
     FINISHED_ABORTED = enum.auto()   # client abort / engine shutdown
+    FINISHED_EXPORTED = enum.auto()  # prefilled; KV handed to another engine
 
     @property
     def finished(self) -> bool:
@@ -28,6 +29,7 @@ class RequestStatus(enum.Enum):
             RequestStatus.FINISHED_STOPPED,
             RequestStatus.FINISHED_LENGTH,
             RequestStatus.FINISHED_ABORTED,
+            RequestStatus.FINISHED_EXPORTED,
         )
 
 
@@ -35,6 +37,7 @@ FINISH_REASON = {
     RequestStatus.FINISHED_STOPPED: "stop",
     RequestStatus.FINISHED_LENGTH: "length",
     RequestStatus.FINISHED_ABORTED: "abort",
+    RequestStatus.FINISHED_EXPORTED: "kv_export",
 }
 
 
@@ -65,6 +68,11 @@ class Request:
         self.lora_id = 0
         # guided decoding (engine/guided.py): per-request JSON machine
         self.guided_machine = None
+        # prefill/decode disaggregation (engine/kv_transfer.py): export the
+        # KV after the first token / the payload still to be imported
+        # (cleared once its pages are in this engine's pool)
+        self.kv_export = False
+        self.kv_import = None
         # scheduler arrival sequence (set by Scheduler.add_request)
         self.arrival_seq = 0
         # prefix caching: tokens whose KV was found resident at allocate
@@ -153,3 +161,5 @@ class RequestOutput:
     text_delta: str = ""
     output_text: str = ""
     logprobs: Optional[list] = None
+    # KVPayload of a request that finished with reason "kv_export"
+    kv_payload: Optional[object] = None

@@ -67,6 +67,8 @@ class Scheduler:
         self.running: List[Request] = []
         # requests whose KV lives in the host-DRAM tier
         self.swapped: List[Request] = []
+        # waiting requests that carry a KV payload to import
+        self.num_pending_imports = 0
 
     # -- queue ops -----------------------------------------------------------
     def _queue_key(self, request: Request):
@@ -87,12 +89,17 @@ class Scheduler:
             return
         request.arrival_seq = self._arrival_seq
         self._arrival_seq += 1
+        if request.kv_import is not None:
+            self.num_pending_imports += 1
         self._enqueue(request)
 
     def abort_request(self, request_id: str) -> Optional[Request]:
         for q in (self.waiting, self.running, self.swapped):
             for r in list(q):
                 if r.request_id == request_id:
+                    if r.kv_import is not None:
+                        r.kv_import = None
+                        self.num_pending_imports -= 1
                     r.status = RequestStatus.FINISHED_ABORTED
                     r.is_finished = True
                     q.remove(r)
@@ -126,6 +133,9 @@ class Scheduler:
         token_budget = self.config.max_num_batched_tokens
         while self.waiting:
             req = self.waiting[0]
+            if req.kv_import is not None:
+                # never prefilled: admit_imports() takes it, in queue order
+                break
             # prefix cache: size the chunk from the cached-prefix boundary
             # so budget/allocation cover exactly the tokens that will run
             cached_hint = 0
@@ -176,6 +186,28 @@ class Scheduler:
         for r in batch.requests:
             self.running.append(r)
         return batch
+
+    def admit_imports(self) -> List[Request]:
+        """Admit the KV-import requests at the head of the waiting queue,
+        under the limits of any admission: a seat in ``max_num_seqs`` and
+        free blocks for the imported positions plus the next token. An
+        admitted request has its (private) block table and is RUNNING; the
+        engine fills the pages before the next batch executes."""
+        admitted: List[Request] = []
+        while self.waiting and self.waiting[0].kv_import is not None:
+            req = self.waiting[0]
+            if len(self.running) + 1 > self.config.max_num_seqs:
+                break
+            need = req.kv_import.num_tokens + 1
+            if not self.block_manager.can_allocate(req, need):
+                break
+            self.block_manager.allocate_private(req, need)
+            self.waiting.pop(0)
+            self.num_pending_imports -= 1
+            req.status = RequestStatus.RUNNING
+            self.running.append(req)
+            admitted.append(req)
+        return admitted
 
     def _schedule_decode(self) -> ScheduledBatch:
         batch = ScheduledBatch(is_prefill=False)

@@ -43,6 +43,23 @@ LLM_TPOT_HIST = Histogram(
 LLM_E2E_HIST = Histogram("llm_e2e_request_seconds", "end-to-end request latency")
 LLM_KV_USAGE = Gauge("llm_kv_cache_usage_ratio", "fraction of GPU KV blocks in use")
 LLM_PREEMPTIONS = Counter("llm_preemptions_total", "scheduler preemptions")
+# prefill/decode disaggregation (engine/kv_transfer.py)
+LLM_KV_EXPORTED = Counter(
+    "kv_transfer_exported_requests_total", "requests whose KV was exported"
+)
+LLM_KV_EXPORT_BYTES = Counter(
+    "kv_transfer_exported_bytes_total", "KV page bytes exported"
+)
+LLM_KV_IMPORTED = Counter(
+    "kv_transfer_imported_requests_total", "requests continued from imported KV"
+)
+LLM_KV_IMPORT_BYTES = Counter(
+    "kv_transfer_imported_bytes_total", "KV page bytes imported"
+)
+KV_TRANSFER_FALLBACK = Counter(
+    "kv_transfer_fallback_total",
+    "requests prefilled locally because the prefill pool failed",
+)
 
 
 def get_labeled_histograms(model_name: str):

@@ -516,3 +516,120 @@ def lora_expand_add(
     return torch_ref.lora_expand_add(
         y, tmp, b_stack, scale, ranks, slot_idx, out_offset
     )
+
+
+# -- KV export / import (prefill-decode disaggregation) ----------------------
+
+# device table of the 2L cache base pointers (K0, V0, K1, V1, ...), built the
+# first time a pool is exported from or imported into, keyed by the pointers
+_KV_BASES: dict = {}
+
+
+def _kv_bases(kv_caches) -> torch.Tensor:
+    ptrs = tuple(t.data_ptr() for kv in kv_caches for t in kv)
+    table = _KV_BASES.get(ptrs)
+    if table is None:
+        if len(_KV_BASES) >= 8:
+            _KV_BASES.clear()
+        table = torch.tensor(
+            ptrs, dtype=torch.int64, device=kv_caches[0][0].device
+        )
+        _KV_BASES[ptrs] = table
+    return table
+
+
+def _check_kv_transfer_args(kv_caches, block_ids, unique: bool):
+    """Host-side validation shared by both devices; the kernels trust the
+    ids. Returns the ids as a list of ints."""
+    if not kv_caches:
+        raise ValueError("kv_caches is empty")
+    k0 = kv_caches[0][0]
+    for k, v in kv_caches:
+        for t in (k, v):
+            if t.shape != k0.shape or t.dtype != k0.dtype:
+                raise ValueError("all layers must share one shape and dtype")
+    ids = [int(b) for b in block_ids]
+    num_blocks = k0.shape[0]
+    for b in ids:
+        if not 0 <= b < num_blocks:
+            raise ValueError(
+                f"block id {b} outside [0, {num_blocks})"
+            )
+    if unique and len(set(ids)) != len(ids):
+        raise ValueError("duplicate block id in a scatter")
+    return ids
+
+
+def kv_gather_pages(
+    kv_caches,
+    block_ids,
+    num_tokens: int,
+    out_dtype: Optional[torch.dtype] = None,
+) -> torch.Tensor:
+    """Gather pages ``block_ids`` (a host list) of every layer's K and V
+    into one contiguous [L, 2, n, Hkv, block_size, D] tensor on the pool's
+    device, in one launch. Slots at position ``j*block_size + s >=
+    num_tokens`` are zero bytes, so nothing a previous owner of the last
+    page left behind travels. ``out_dtype=torch.float8_e4m3fn`` on a bf16
+    pool converts exactly as ``reshape_and_cache`` does for an fp8 pool;
+    fp8 -> bf16 is refused."""
+    ids = _check_kv_transfer_args(kv_caches, block_ids, unique=False)
+    k0 = kv_caches[0][0]
+    out_dtype = out_dtype or k0.dtype
+    if out_dtype != k0.dtype and not (
+        k0.dtype == torch.bfloat16 and out_dtype == torch.float8_e4m3fn
+    ):
+        raise ValueError(
+            f"cannot export a {k0.dtype} pool as {out_dtype}: only bf16 -> "
+            "fp8_e4m3 converts"
+        )
+    if not 0 <= num_tokens <= len(ids) * k0.shape[2]:
+        raise ValueError(
+            f"num_tokens {num_tokens} outside the {len(ids)} listed pages"
+        )
+    if not k0.is_cuda:
+        return torch_ref.kv_gather_pages(kv_caches, ids, num_tokens, out_dtype)
+    out = torch.empty(
+        (len(kv_caches), 2, len(ids), *k0.shape[1:]),
+        dtype=out_dtype, device=k0.device,
+    )
+    if ids:
+        _native("kv_gather_pages").kv_gather_pages(
+            out,
+            [t for kv in kv_caches for t in kv],
+            _kv_bases(kv_caches),
+            torch.tensor(ids, dtype=torch.int32).to(k0.device),
+            int(num_tokens),
+        )
+    return out
+
+
+def kv_scatter_pages(kv_caches, block_ids, src: torch.Tensor) -> None:
+    """Write ``src`` ([L, 2, n, Hkv, block_size, D] in the pool's dtype, or
+    the same bytes as uint8) into pages ``block_ids`` (a host list, no
+    duplicates) of every layer's K and V: whole pages, nothing else."""
+    ids = _check_kv_transfer_args(kv_caches, block_ids, unique=True)
+    k0 = kv_caches[0][0]
+    if src.dtype != k0.dtype and src.dtype != torch.uint8:
+        raise ValueError(
+            f"payload dtype {src.dtype} does not match the pool's {k0.dtype}"
+        )
+    want = len(kv_caches) * 2 * len(ids) * k0[0].numel() * k0.element_size()
+    if src.numel() * src.element_size() != want:
+        raise ValueError(
+            f"payload holds {src.numel() * src.element_size()} bytes, the "
+            f"listed pages need {want}"
+        )
+    if src.device != k0.device or not src.is_contiguous():
+        raise ValueError("src must be contiguous and on the pool's device")
+    if not ids:
+        return
+    if not k0.is_cuda:
+        torch_ref.kv_scatter_pages(kv_caches, ids, src)
+        return
+    _native("kv_scatter_pages").kv_scatter_pages(
+        [t for kv in kv_caches for t in kv],
+        _kv_bases(kv_caches),
+        torch.tensor(ids, dtype=torch.int32).to(k0.device),
+        src.view(k0.dtype),
+    )

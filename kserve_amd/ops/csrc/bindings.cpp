@@ -72,6 +72,10 @@ hipError_t ks_lora_shrink(void*, const void*, const void*, const void*,
 hipError_t ks_lora_expand_add(void*, const void*, const void*, const void*,
                               const void*, const void*, int, int, int, int,
                               long, int, hipStream_t);
+hipError_t ks_kv_gather_pages(void*, const void*, const void*, int, int, long,
+                              int, int, int, int, hipStream_t);
+hipError_t ks_kv_scatter_pages(const void*, const void*, const void*, int, int,
+                               long, hipStream_t);
 }
 
 namespace {
@@ -619,6 +623,90 @@ void lora_expand_add(at::Tensor& y, at::Tensor& tmp, at::Tensor& b_stack,
             "lora_expand_add");
 }
 
+// Shared checks of the KV export/import ops. `caches` is K0, V0, K1, V1, ...
+// and `bases` the device table of their base pointers in the same order
+// (built once by the caller); returns the bytes of one page of one tensor.
+int64_t check_kv_transfer(const std::vector<at::Tensor>& caches,
+                          at::Tensor& bases, at::Tensor& block_ids) {
+  TORCH_CHECK(!caches.empty() && caches.size() % 2 == 0,
+              "caches must list K and V of every layer");
+  const at::Tensor& first = caches[0];
+  TORCH_CHECK(first.dim() == 4, "cache must be [blocks, Hkv, block, D]");
+  for (const at::Tensor& c : caches) {
+    CHECK_KV_CACHE(c);
+    TORCH_CHECK(c.scalar_type() == first.scalar_type() &&
+                    c.sizes() == first.sizes() &&
+                    c.device() == first.device(),
+                "all layers must share one shape, dtype and device");
+    TORCH_CHECK((uintptr_t)c.data_ptr() % 16 == 0,
+                "caches must be 16-byte aligned");
+  }
+  TORCH_CHECK(bases.scalar_type() == at::kLong && bases.is_cuda() &&
+                  bases.is_contiguous() && bases.dim() == 1 &&
+                  bases.size(0) == (int64_t)caches.size(),
+              "bases must be a contiguous int64 [2L] GPU tensor");
+  TORCH_CHECK(block_ids.scalar_type() == at::kInt && block_ids.is_cuda() &&
+                  block_ids.is_contiguous() && block_ids.dim() == 1,
+              "block_ids must be a contiguous int32 [n] GPU tensor");
+  const int64_t page_bytes = first.size(1) * first.size(2) * first.size(3) *
+                             (int64_t)first.element_size();
+  TORCH_CHECK(page_bytes % 16 == 0, "page bytes must be a multiple of 16");
+  return page_bytes;
+}
+
+void kv_gather_pages(at::Tensor& out, std::vector<at::Tensor> caches,
+                     at::Tensor& bases, at::Tensor& block_ids,
+                     int64_t num_tokens) {
+  // out [L, 2, n, Hkv, block, D] <- the listed pages of every cache; slots
+  // at position >= num_tokens zeroed. out fp8 from bf16 pools converts.
+  int64_t page_bytes = check_kv_transfer(caches, bases, block_ids);
+  const at::Tensor& first = caches[0];
+  CHECK_KV_CACHE(out);
+  const bool convert = first.scalar_type() == at::kBFloat16 &&
+                       out.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(convert || out.scalar_type() == first.scalar_type(),
+              "payload dtype must equal the pool dtype, or be fp8_e4m3 for a "
+              "bf16 pool (fp8 -> bf16 is refused)");
+  TORCH_CHECK((uintptr_t)out.data_ptr() % 16 == 0,
+              "out must be 16-byte aligned");
+  if (convert) page_bytes /= 2;
+  const int64_t row_bytes = first.size(3) * (int64_t)out.element_size();
+  TORCH_CHECK(row_bytes % 16 == 0, "head_dim row must be a multiple of 16 B");
+  const int64_t n = block_ids.size(0);
+  const int64_t block_size = first.size(2);
+  TORCH_CHECK(num_tokens >= 0 && num_tokens <= n * block_size,
+              "num_tokens outside the listed pages");
+  TORCH_CHECK(out.numel() == (int64_t)caches.size() * n * first.size(1) *
+                                 block_size * first.size(3),
+              "out must hold exactly [L, 2, n, Hkv, block, D] elements");
+  check_hip(ks_kv_gather_pages(out.data_ptr(), bases.data_ptr(),
+                               block_ids.data_ptr(), (int)caches.size(),
+                               (int)n, (long)page_bytes, (int)row_bytes,
+                               (int)block_size, (int)num_tokens,
+                               convert ? 1 : 0, current_stream()),
+            "kv_gather_pages");
+}
+
+void kv_scatter_pages(std::vector<at::Tensor> caches, at::Tensor& bases,
+                      at::Tensor& block_ids, at::Tensor& src) {
+  // the listed pages of every cache <- src [L, 2, n, Hkv, block, D]
+  const int64_t page_bytes = check_kv_transfer(caches, bases, block_ids);
+  const at::Tensor& first = caches[0];
+  CHECK_KV_CACHE(src);
+  TORCH_CHECK(src.scalar_type() == first.scalar_type(),
+              "payload dtype must equal the pool dtype");
+  TORCH_CHECK((uintptr_t)src.data_ptr() % 16 == 0,
+              "src must be 16-byte aligned");
+  const int64_t n = block_ids.size(0);
+  TORCH_CHECK(src.numel() == (int64_t)caches.size() * n * first.size(1) *
+                                 first.size(2) * first.size(3),
+              "src must hold exactly [L, 2, n, Hkv, block, D] elements");
+  check_hip(ks_kv_scatter_pages(src.data_ptr(), bases.data_ptr(),
+                                block_ids.data_ptr(), (int)caches.size(),
+                                (int)n, (long)page_bytes, current_stream()),
+            "kv_scatter_pages");
+}
+
 void gemm8(at::Tensor& d, at::Tensor& a, at::Tensor& w, int64_t swizzle) {
   // EXPERIMENTAL (see gemm8.hip header): not used by ops.linear dispatch
   CHECK_BF16_CONTIG(d);
@@ -681,6 +769,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("y"), pybind11::arg("tmp"), pybind11::arg("b_stack"),
         pybind11::arg("scale"), pybind11::arg("ranks"),
         pybind11::arg("slot_idx"), pybind11::arg("out_offset") = 0);
+  m.def("kv_gather_pages", &kv_gather_pages,
+        "gather a request's KV pages of every layer into one buffer");
+  m.def("kv_scatter_pages", &kv_scatter_pages,
+        "scatter a gathered KV buffer into the listed pages of every layer");
   m.def("gemm8", &gemm8,
         "EXPERIMENTAL 8-phase 256x256 MFMA GEMM (round-2 candidate)");
   m.def("mfma_probe", &mfma_probe, "MFMA layout probe (tests)");

@@ -398,3 +398,45 @@ def lora_expand_add(
             cur + float(scale[s]) * d
         ).to(y.dtype)
     return y
+
+
+def _kv_pages_u8(t: torch.Tensor) -> torch.Tensor:
+    """Byte view [num_blocks, Hkv, block_size, D*itemsize] of a cache."""
+    return t.view(torch.uint8)
+
+
+def kv_gather_pages(kv_caches, block_ids, num_tokens: int, out_dtype=None):
+    """Pages ``block_ids`` of every layer's K and V as one contiguous
+    [L, 2, n, Hkv, block_size, D] tensor. Slots at logical position
+    ``j*block_size + s >= num_tokens`` are zero bytes. ``out_dtype`` fp8 on
+    a bf16 pool converts (the cast reshape_and_cache applies)."""
+    ids = torch.as_tensor(list(block_ids), dtype=torch.long)
+    k0 = kv_caches[0][0]
+    out_dtype = out_dtype or k0.dtype
+    bs = k0.shape[2]
+    planes = []
+    for k, v in kv_caches:
+        for t in (k, v):
+            if out_dtype == t.dtype:
+                planes.append(_kv_pages_u8(t)[ids])
+            else:
+                planes.append(_kv_pages_u8(t[ids].to(out_dtype)))
+    out = torch.stack(planes).reshape(
+        len(kv_caches), 2, len(ids), k0.shape[1], bs, -1
+    )
+    pos = torch.arange(len(ids) * bs).reshape(len(ids), 1, bs, 1)
+    out = out.masked_fill(pos >= num_tokens, 0)
+    return out.contiguous().view(out_dtype)
+
+
+def kv_scatter_pages(kv_caches, block_ids, src: torch.Tensor) -> None:
+    """Inverse of kv_gather_pages: writes the listed pages of every cache,
+    whole pages, and nothing else."""
+    ids = torch.as_tensor(list(block_ids), dtype=torch.long)
+    k0 = kv_caches[0][0]
+    src = src.contiguous().view(torch.uint8).reshape(
+        len(kv_caches), 2, len(ids), k0.shape[1], k0.shape[2], -1
+    )
+    for layer, (k, v) in enumerate(kv_caches):
+        _kv_pages_u8(k)[ids] = src[layer, 0]
+        _kv_pages_u8(v)[ids] = src[layer, 1]

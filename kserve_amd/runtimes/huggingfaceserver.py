@@ -138,7 +138,9 @@ def build_model(args):
                     raise ValueError(f"--lora-modules expects name=path, got {spec!r}")
                 lora_modules[name] = path
         return LLMModel(
-            args.model_name, cfg, tokenizer=tokenizer, lora_modules=lora_modules
+            args.model_name, cfg, tokenizer=tokenizer, lora_modules=lora_modules,
+            role=getattr(args, "role", "both"),
+            prefill_endpoint=getattr(args, "prefill_endpoint", None),
         )
     if backend == "hf":
         from kserve_amd.runtimes.hf_generative import HFGenerativeModel
@@ -191,6 +193,14 @@ def build_parser():
     parser.add_argument("--speculative-ngram", dest="speculative_ngram",
                         type=int, default=0)
     parser.add_argument("--enable-lora", dest="enable_lora", action="store_true")
+    # prefill/decode disaggregation (LLMInferenceService prefill workload):
+    # "prefill" also serves POST /v1/kv/prefill; "decode" with
+    # --prefill-endpoint fetches each prompt's KV from that server and
+    # prefills locally whenever it fails
+    parser.add_argument("--role", dest="role", default="both",
+                        choices=["both", "prefill", "decode"])
+    parser.add_argument("--prefill-endpoint", dest="prefill_endpoint",
+                        default=None, help="base URL of a --role=prefill server")
     parser.add_argument(
         "--lora-modules", dest="lora_modules", nargs="*", default=[],
         help="name=path pairs; each name becomes a served model id",
@@ -198,17 +208,28 @@ def build_parser():
     return parser
 
 
-def main(argv=None):
+def make_server(args, model):
+    """The ModelServer main() starts for ``model``; a prefill-role model
+    gets its ``POST /v1/kv/prefill`` route mounted on the server's app."""
     from kserve_amd.model_server import ModelServer
 
-    args = build_parser().parse_args(argv)
-    configure_logging()
-    model = build_model(args)
-    ModelServer(
+    server = ModelServer(
         http_port=args.http_port,
         grpc_port=args.grpc_port,
         enable_grpc=args.enable_grpc,
-    ).start([model])
+    )
+    if getattr(model, "role", "both") == "prefill":
+        from kserve_amd.runtimes.llm_model import register_kv_prefill_route
+
+        register_kv_prefill_route(server.app, model)
+    return server
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    configure_logging()
+    model = build_model(args)
+    make_server(args, model).start([model])
 
 
 if __name__ == "__main__":

@@ -86,8 +86,22 @@ class LLMModel(OpenAIModel):
         engine_config: EngineConfig,
         tokenizer=None,
         lora_modules=None,
+        role: str = "both",
+        prefill_endpoint: Optional[str] = None,
+        http_client=None,
     ):
         super().__init__(name)
+        if role not in ("both", "prefill", "decode"):
+            raise ValueError(f"unknown role {role!r}")
+        # prefill/decode disaggregation: a "prefill" server also answers
+        # POST /v1/kv/prefill (register_kv_prefill_route); a "decode" server
+        # with a prefill endpoint asks that peer for each prompt's KV and
+        # falls back to its own prefill whenever the peer fails
+        self.role = role
+        self.prefill_endpoint = (
+            prefill_endpoint.rstrip("/") if prefill_endpoint else None
+        )
+        self._kv_http_client = http_client
         self.engine = True  # ModelServer awaits start_engine()
         self.tokenizer = tokenizer
         # name -> adapter dir; each name is served as its own model id
@@ -116,6 +130,96 @@ class LLMModel(OpenAIModel):
 
     async def healthy(self) -> bool:
         return self.ready and self.async_engine.is_running
+
+    # -- prefill/decode disaggregation -----------------------------------------
+    _KV_SAMPLING_FIELDS = (
+        "temperature", "top_p", "top_k", "min_p", "logit_bias", "seed",
+        "logprobs", "presence_penalty", "frequency_penalty",
+        "repetition_penalty", "priority",
+    )
+
+    async def kv_prefill(self, body: dict) -> bytes:
+        """Prefill-role entry: prefill the prompt, sample its first token
+        and return the KV payload bytes."""
+        import asyncio
+
+        ids = body.get("prompt_token_ids")
+        if not isinstance(ids, list) or not ids or not all(
+            isinstance(t, int) for t in ids
+        ):
+            raise InvalidInput("prompt_token_ids must be a list of token ids")
+        fields = body.get("sampling") or {}
+        kw = {k: fields[k] for k in self._KV_SAMPLING_FIELDS if k in fields}
+        if kw.get("logit_bias"):
+            kw["logit_bias"] = {
+                int(k): float(v) for k, v in kw["logit_bias"].items()
+            }
+        try:
+            sp = SamplingParams(max_tokens=1, **kw)
+            out = await self.async_engine.generate_full(
+                ids, sp, kv_export=True
+            )
+        except (TypeError, ValueError) as e:
+            raise InvalidInput(str(e)) from e
+        if out is None or out.kv_payload is None:
+            raise InvalidInput("request ended without a KV payload")
+        return await asyncio.to_thread(out.kv_payload.to_bytes)
+
+    async def _remote_prefill(self, ids: List[int], sp: SamplingParams):
+        """Decode role: fetch the prompt's KV from the prefill pool. Returns
+        a KVPayload, or None when this request is prefilled locally: always
+        for requests the transfer refuses (LoRA, guided decoding), and
+        counted in ``kv_transfer_fallback_total`` when the peer is
+        unreachable, answers non-200 or sends a payload that fails
+        validation. A decode pod never fails a request because the prefill
+        pool is down."""
+        if self.role != "decode" or not self.prefill_endpoint:
+            return None
+        if sp.lora_name or sp.guided_choice or sp.response_format in (
+            "json", "json_object", "json_schema"
+        ):
+            return None
+        import asyncio
+        import dataclasses
+
+        import httpx
+
+        from kserve_amd.engine.kv_transfer import KVPayload
+        from kserve_amd.metrics import KV_TRANSFER_FALLBACK
+
+        # everything that touches the peer or its answer is inside the
+        # try: whatever goes wrong there, the request is served locally
+        try:
+            if self._kv_http_client is None:
+                self._kv_http_client = httpx.AsyncClient(
+                    timeout=httpx.Timeout(60.0)
+                )
+            spd = dataclasses.asdict(sp)
+            r = await self._kv_http_client.post(
+                self.prefill_endpoint + "/v1/kv/prefill",
+                json={
+                    "prompt_token_ids": list(ids),
+                    "sampling": {
+                        k: spd[k] for k in self._KV_SAMPLING_FIELDS
+                    },
+                },
+            )
+            if r.status_code != 200:
+                raise ValueError(f"prefill peer answered {r.status_code}")
+            # a payload can be hundreds of MB: parse and copy it off the
+            # event loop so other requests keep streaming
+            payload = await asyncio.to_thread(KVPayload.from_bytes, r.content)
+            # every refusal add_request would raise for this payload
+            self.async_engine.engine.check_kv_transfer(
+                list(ids), sp, False, payload
+            )
+            return payload
+        except Exception as e:  # noqa: BLE001 - never fail the request here
+            KV_TRANSFER_FALLBACK.inc()
+            logger.warning(
+                "remote prefill failed, prefilling locally: %r", e
+            )
+            return None
 
     # -- prompt handling -----------------------------------------------------
     def _encode_prompt(self, prompt) -> List[int]:
@@ -188,12 +292,14 @@ class LLMModel(OpenAIModel):
                 jobs.append((i, j, ids, sp_j))
         import asyncio as _asyncio
 
+        async def run(ids, sp_j):
+            return await self.async_engine.generate_full(
+                ids, sp_j, kv_import=await self._remote_prefill(ids, sp_j)
+            )
+
         try:
             outs = await _asyncio.gather(
-                *(
-                    self.async_engine.generate_full(ids, sp_j)
-                    for (_, _, ids, sp_j) in jobs
-                )
+                *(run(ids, sp_j) for (_, _, ids, sp_j) in jobs)
             )
         except ValueError as e:
             raise InvalidInput(str(e)) from e
@@ -251,7 +357,8 @@ class LLMModel(OpenAIModel):
     ) -> AsyncIterator[Completion]:
         ids = self._encode_prompt(prompt)
         completion_tokens = 0
-        async for out in self.async_engine.generate(ids, sp):
+        kv = await self._remote_prefill(ids, sp)
+        async for out in self.async_engine.generate(ids, sp, kv_import=kv):
             text = out.text_delta or (
                 ""
                 if self.tokenizer is not None
@@ -291,7 +398,9 @@ class LLMModel(OpenAIModel):
         if request.stream:
             return self._stream_chat(ids, sp, request)
         try:
-            out = await self.async_engine.generate_full(ids, sp)
+            out = await self.async_engine.generate_full(
+                ids, sp, kv_import=await self._remote_prefill(ids, sp)
+            )
         except ValueError as e:
             raise InvalidInput(str(e)) from e
         text = out.output_text if out.output_text else self._decode(out.output_token_ids)
@@ -316,7 +425,8 @@ class LLMModel(OpenAIModel):
     ) -> AsyncIterator[ChatCompletionChunk]:
         first = True
         completion_tokens = 0
-        async for out in self.async_engine.generate(ids, sp):
+        kv = await self._remote_prefill(ids, sp)
+        async for out in self.async_engine.generate(ids, sp, kv_import=kv):
             completion_tokens += len(out.new_token_ids)
             delta = ChatCompletionChunkDelta(
                 role="assistant" if first else None,
@@ -349,3 +459,25 @@ class LLMModel(OpenAIModel):
                     total_tokens=len(ids) + completion_tokens,
                 ),
             )
+
+
+def register_kv_prefill_route(app, model: LLMModel) -> None:
+    """Mount ``POST /v1/kv/prefill`` on a prefill-role server: JSON in
+    (``prompt_token_ids`` and the ``sampling`` fields), the KV payload out
+    as ``application/octet-stream``."""
+    from fastapi import Request
+    from fastapi.responses import JSONResponse, Response
+
+    async def kv_prefill(raw_request: Request):
+        try:
+            body = await raw_request.json()
+            if not isinstance(body, dict):
+                raise InvalidInput("body must be a JSON object")
+            blob = await model.kv_prefill(body)
+        except (InvalidInput, ValueError) as e:
+            return JSONResponse(status_code=400, content={"error": str(e)})
+        return Response(content=blob, media_type="application/octet-stream")
+
+    # the module's postponed annotations cannot see the local import
+    kv_prefill.__annotations__ = {"raw_request": Request}
+    app.add_api_route("/v1/kv/prefill", kv_prefill, methods=["POST"])
