@@ -31,6 +31,7 @@ KERNEL_SOURCES = [
     "attention_decode.hip",
     "attention_prefill.hip",
     "sampling.hip",
+    "logit_process.hip",
     "skinny_gemm.hip",
     "w8_gemm.hip",
     "w4_gemm.hip",

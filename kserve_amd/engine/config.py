@@ -258,6 +258,14 @@ class SchedulerConfig:
     # draft-MODEL speculation: tokens proposed per round by the draft
     # model configured in EngineConfig.draft_model. 0 disables.
     speculative_k: int = 0
+    # in-graph logit processors (engine/logit_state.py): number of requests
+    # that can hold device state for presence/frequency/repetition penalties,
+    # logit_bias and min_p at one time, so that batches with such requests
+    # keep their multi-step windows. 0 (off): such a request puts its whole
+    # batch on single steps with host-side processors. Memory:
+    # slots x vocab_size x 4 B (+ slots x 4 KB for the bias lists); 64 slots
+    # at vocab 128256 are 33 MB.
+    logit_processor_slots: int = 0
 
 
 @dataclass

@@ -17,6 +17,7 @@ from kserve_amd import ops
 from kserve_amd.engine.config import EngineConfig
 from kserve_amd.engine.detokenizer import Detokenizer
 from kserve_amd.engine.kv_transfer import KVPayload, dtype_name
+from kserve_amd.engine.logit_state import wants_processors
 from kserve_amd.engine.model_runner import ModelRunner
 from kserve_amd.engine.request import Request, RequestOutput, RequestStatus
 from kserve_amd.engine.sampling_params import SamplingParams
@@ -508,6 +509,8 @@ class LLMEngine:
 
     def abort_request(self, request_id: str):
         self.scheduler.abort_request(request_id)
+        if self.runner.logit_state is not None:
+            self.runner.logit_state.release(request_id)
 
     def has_unfinished(self) -> bool:
         return self.scheduler.has_unfinished()
@@ -539,22 +542,35 @@ class LLMEngine:
             # the logits or token history on the host each step disqualifies
             window_ok = all(
                 r.sampling_params.logprobs is None
-                and r.sampling_params.presence_penalty == 0.0
-                and r.sampling_params.frequency_penalty == 0.0
-                and r.sampling_params.repetition_penalty == 1.0
-                and not r.sampling_params.logit_bias
-                and r.sampling_params.min_p == 0.0
                 and r.lora_id == 0
                 and r.guided_machine is None
                 for r in batch.requests
             )
-            pure_greedy = window_ok and all(
+            # logit processors (penalties, logit_bias, min_p) need the token
+            # history too, but as a histogram that can live on the device:
+            # with logit_processor_slots > 0 their requests take a state
+            # slot and the window runs the processed graph variant. Without
+            # the option, or when a request cannot get a slot, the whole
+            # batch takes single steps with the host Sampler, as before.
+            lp_reqs = [
+                r for r in batch.requests
+                if wants_processors(r.sampling_params)
+            ]
+            pp = comm.get_state().pp_size
+            processed = False
+            if lp_reqs and window_ok:
+                processed = (
+                    sched.multi_step > 1
+                    and pp == 1
+                    and self._acquire_processor_slots(lp_reqs)
+                )
+                window_ok = processed
+            pure_greedy = window_ok and not lp_reqs and all(
                 r.sampling_params.greedy for r in batch.requests
             )
             # speculative decoding (prompt-lookup): draft from the request's
             # own context, verify k+1 positions in ONE forward through the
             # paged-context prefill path; exact greedy outputs by construction
-            pp = comm.get_state().pp_size
             if sched.speculative_ngram > 0 and pure_greedy and pp == 1:
                 k_cap = (
                     self.scheduler.reserve_decode_window(
@@ -591,7 +607,7 @@ class LLMEngine:
                 )
             if k > 1:
                 return self._run_decode_window(
-                    batch, k, sampled=not pure_greedy
+                    batch, k, sampled=not pure_greedy, processed=processed
                 )
             logits = self.runner.execute_decode(batch, self.scheduler.block_manager)
         # advance computed-token counters for executed tokens
@@ -852,12 +868,36 @@ class LLMEngine:
                 self.draft.release(req.request_id)
         return outputs
 
+    def _acquire_processor_slots(self, lp_reqs: List[Request]) -> bool:
+        """True when every request with logit processors holds a state slot
+        (taking free ones as needed), i.e. the batch may run a processed
+        window. False leaves the batch on the host path; slots already held
+        are kept for a later step."""
+        state = self.runner.logit_state
+        if state is None:
+            return False
+        if not all(state.eligible(r.sampling_params) for r in lp_reqs):
+            return False
+        ok = True
+        for r in lp_reqs:
+            if state.acquire(r) is None:
+                ok = False
+        return ok
+
     def _run_decode_window(
-        self, batch, k: int, sampled: bool = False
+        self, batch, k: int, sampled: bool = False, processed: bool = False
     ) -> List[RequestOutput]:
-        tokens_k = self.runner.multi_step_decode(
-            batch, self.scheduler.block_manager, k, sampled=sampled
-        )
+        if processed:
+            # single steps sampled on the host since the last window (at
+            # least the token from the prefill logits): one launch
+            self.runner.logit_state.catch_up(batch.requests)
+            tokens_k = self.runner.multi_step_decode(
+                batch, self.scheduler.block_manager, k, processed=True
+            )
+        else:
+            tokens_k = self.runner.multi_step_decode(
+                batch, self.scheduler.block_manager, k, sampled=sampled
+            )
         # ONE RequestOutput per request per window (streaming consumers get
         # k-token chunks); per-token python only for stop conditions
         cols = tokens_k.t().tolist()  # [n][k]
@@ -894,6 +934,9 @@ class LLMEngine:
             if req.is_finished:
                 finished.append(req)
                 LLM_E2E_HIST.observe(now - req.arrival_time)
+            elif processed:
+                # alive, so it took all k tokens, and the graph counted them
+                self.runner.logit_state.mark_synced(req)
             n_tokens += len(col)
             outputs.append(
                 RequestOutput(

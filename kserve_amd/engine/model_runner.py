@@ -71,6 +71,19 @@ class ModelRunner:
         )
         # multi-LoRA (set by LLMEngine.register_lora)
         self.lora_manager = None
+        # in-graph logit processors (opt-in): per-request device state and
+        # the graph variant that reads it (captured lazily per bucket)
+        self.logit_state = None
+        self._lp_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self._lp_pin: Optional[Dict[str, torch.Tensor]] = None
+        if config.scheduler.logit_processor_slots > 0:
+            from kserve_amd.engine.logit_state import LogitProcessorState
+
+            self.logit_state = LogitProcessorState(
+                config.scheduler.logit_processor_slots,
+                config.model.vocab_size,
+                self.device,
+            )
 
     # -- KV cache -----------------------------------------------------------
     def profile_and_allocate_kv(self) -> int:
@@ -348,6 +361,8 @@ class ModelRunner:
 
     def release_request(self, request_id: str):
         self._bt_cache.pop(request_id, None)
+        if self.logit_state is not None:
+            self.logit_state.release(request_id)
 
     def prepare_decode(
         self, batch: ScheduledBatch, block_manager: BlockManager
@@ -525,6 +540,19 @@ class ModelRunner:
             "sampled": {},
             "sampled_rand": {},
         }
+        if self.logit_state is not None:
+            # per-row logit-processor params (processed-window variant):
+            # slot -1 = row without processors / graph padding
+            self._graph_buffers.update({
+                "lp_slots": torch.full(
+                    (max_bs,), -1, dtype=torch.int32, device=dev
+                ),
+                "presence": torch.zeros(max_bs, dtype=torch.float32, device=dev),
+                "frequency": torch.zeros(max_bs, dtype=torch.float32, device=dev),
+                "repetition": torch.ones(max_bs, dtype=torch.float32, device=dev),
+                "min_p": torch.zeros(max_bs, dtype=torch.float32, device=dev),
+                "lp_sampled": {},
+            })
         torch.cuda.synchronize()
         pool = None
         from kserve_amd import ops as _ops
@@ -626,6 +654,84 @@ class ModelRunner:
         self._sampled_graphs[bs] = g
         buf["sampled_rand"][bs] = sampled
         logger.info("Captured sampled-decode hipGraph for batch size %d", bs)
+        return g
+
+    def _ensure_processed_graph(self, bs: int) -> torch.cuda.CUDAGraph:
+        """Capture (once, lazily) the logit-processor variant for a bucket:
+        the sampled body with ``logit_process`` applied in place to the
+        logits before sampling (rows with ``lp_slots == -1`` are skipped),
+        the min-p form of the fused sampler, and ``token_count_add`` of the
+        sampled tokens afterwards, so the penalties of step k+1 see the
+        token of step k with no host involvement. One variant serves greedy
+        and sampled batches (``greedy_mask``). The state buffers are read
+        through pointers captured here and are never reallocated."""
+        g = self._lp_graphs.get(bs)
+        if g is not None:
+            return g
+        from kserve_amd import ops as _ops
+
+        buf = self._graph_buffers
+        st = self.logit_state
+        bsz = self.config.cache.block_size
+
+        def body():
+            pos = buf["positions"][:bs]
+            bt = buf["block_tables"][:bs]
+            blk = torch.gather(bt, 1, (pos // bsz).unsqueeze(1)).squeeze(1)
+            slot = (blk * bsz + (pos % bsz).to(torch.int32)).to(torch.int32)
+            meta = AttentionMetadata(
+                is_prefill=False,
+                slot_mapping=slot,
+                block_tables=bt,
+                context_lens=buf["context_lens"][:bs],
+            )
+            hidden = self.model(
+                buf["input_ids"][:bs], pos, self.kv_caches, meta
+            )
+            logits = self.model.compute_logits(hidden)
+            lp_slots = buf["lp_slots"][:bs]
+            _ops.logit_process(
+                logits, st.counts, lp_slots, buf["presence"][:bs],
+                buf["frequency"][:bs], buf["repetition"][:bs],
+                st.bias_ids, st.bias_vals, st.bias_len, out=logits,
+            )
+            greedy = _ops.greedy_sample(logits)
+            rand = torch.empty(bs, dtype=torch.int64, device=logits.device)
+            _ops.topk_topp_minp_sample_into(
+                rand, logits, buf["temps"][:bs], buf["top_p"][:bs],
+                buf["top_k"][:bs], buf["min_p"][:bs], buf["seeds"][:bs],
+            )
+            sampled = torch.where(buf["greedy_mask"][:bs], greedy, rand)
+            _ops.token_count_add(st.counts, lp_slots, sampled)
+            buf["input_ids"][:bs].copy_(sampled)
+            buf["positions"][:bs].add_(1)
+            buf["context_lens"][:bs].add_(1)
+            buf["seeds"][:bs].add_(self._SEED_PRIME)
+            return sampled
+
+        # the warm-up run really executes: run it as all-padding (scratch
+        # block 0, no processor slots) so it writes no live KV page and
+        # counts no token, then let the caller stage real inputs
+        buf["input_ids"][:bs].zero_()
+        buf["positions"][:bs].zero_()
+        buf["context_lens"][:bs].fill_(1)
+        buf["block_tables"][:bs].zero_()
+        buf["lp_slots"][:bs].fill_(-1)
+        buf["greedy_mask"][:bs].fill_(True)
+        buf["temps"][:bs].fill_(1.0)
+        buf["top_p"][:bs].fill_(1.0)
+        buf["top_k"][:bs].zero_()
+        buf["min_p"][:bs].zero_()
+        body()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, pool=self._graph_pool):
+            sampled = body()
+        self._lp_graphs[bs] = g
+        buf["lp_sampled"][bs] = sampled
+        logger.info(
+            "Captured logit-processor decode hipGraph for batch size %d", bs
+        )
         return g
 
     def _lora_graphable(self) -> bool:
@@ -764,10 +870,49 @@ class ModelRunner:
         )
         return n
 
-    def _stage_sampling_params(self, bucket: int, requests) -> None:
+    def _stage_sampling_params(
+        self, bucket: int, requests, processed: bool = False
+    ) -> None:
         """Stage per-request sampling params into the static graph buffers
-        (pinned → device, one async copy per tensor)."""
+        (pinned → device, one async copy per tensor). ``processed`` also
+        stages the logit-processor rows: the request's state slot (-1 for a
+        request without one), its penalties and min_p; padding rows get
+        slot -1, penalties 0, repetition 1, min_p 0."""
         import numpy as np
+
+        if processed:
+            if self._lp_pin is None:
+                max_bs = self._graph_buffers["lp_slots"].shape[0]
+                self._lp_pin = {
+                    "lp_slots": torch.full(
+                        (max_bs,), -1, dtype=torch.int32, pin_memory=True
+                    ),
+                    "presence": torch.zeros(max_bs, dtype=torch.float32, pin_memory=True),
+                    "frequency": torch.zeros(max_bs, dtype=torch.float32, pin_memory=True),
+                    "repetition": torch.ones(max_bs, dtype=torch.float32, pin_memory=True),
+                    "min_p": torch.zeros(max_bs, dtype=torch.float32, pin_memory=True),
+                }
+            lpin = self._lp_pin
+            ln = {k: v.numpy() for k, v in lpin.items()}
+            st = self.logit_state
+            for i, r in enumerate(requests):
+                sp = r.sampling_params
+                ln["lp_slots"][i] = st.slot_of(r.request_id)
+                ln["presence"][i] = sp.presence_penalty
+                ln["frequency"][i] = sp.frequency_penalty
+                ln["repetition"][i] = sp.repetition_penalty
+                ln["min_p"][i] = sp.min_p
+            n = len(requests)
+            if n < bucket:
+                ln["lp_slots"][n:bucket] = -1
+                ln["presence"][n:bucket] = 0.0
+                ln["frequency"][n:bucket] = 0.0
+                ln["repetition"][n:bucket] = 1.0
+                ln["min_p"][n:bucket] = 0.0
+            for key, t in lpin.items():
+                self._graph_buffers[key][:bucket].copy_(
+                    t[:bucket], non_blocking=True
+                )
 
         if self._sample_pin is None or self._sample_pin["temps"].shape[0] < bucket:
             max_bs = self._graph_buffers["temps"].shape[0]
@@ -812,19 +957,32 @@ class ModelRunner:
 
     @torch.no_grad()
     def multi_step_decode(
-        self, batch, block_manager, k_steps: int, sampled: bool = False
+        self, batch, block_manager, k_steps: int, sampled: bool = False,
+        processed: bool = False,
     ) -> torch.Tensor:
         """Run ``k_steps`` decode iterations with the sampled token fed back
         on-GPU (graph path: pure replays, zero host work in the loop).
         ``sampled=True`` uses the in-graph temperature/top-k/top-p variant;
-        default is the greedy graph. Caller must have reserved KV capacity
-        for the whole window. Returns host int64 [k_steps, n]."""
+        default is the greedy graph. ``processed=True`` uses the
+        logit-processor variant (bias, penalties and min-p from
+        ``logit_state``, token counts updated per step; it covers greedy and
+        sampled rows, so ``sampled`` is not consulted); the caller has
+        acquired the slots and caught the counts up. Caller must have
+        reserved KV capacity for the whole window. Returns host int64
+        [k_steps, n]."""
         n = len(batch.requests)
         bucket = None
         if self.is_cuda and self._graphs and not self.config.enforce_eager:
             bucket = self._graph_bucket(n)
         if bucket is not None:
-            if sampled:
+            if processed:
+                # before staging: the capture's warm-up run uses the buffers
+                g = self._ensure_processed_graph(bucket)
+                self._stage_sampling_params(
+                    bucket, batch.requests, processed=True
+                )
+                out_dev = self._graph_buffers["lp_sampled"][bucket]
+            elif sampled:
                 g = self._ensure_sampled_graph(bucket)
                 self._stage_sampling_params(bucket, batch.requests)
                 out_dev = self._graph_buffers["sampled_rand"][bucket]
@@ -847,7 +1005,7 @@ class ModelRunner:
                 g.replay()
                 out_host[k].copy_(out_dev[:n], non_blocking=True)
             torch.cuda.synchronize()
-            if sampled:
+            if sampled or processed:
                 self._rng_step += k_steps
             return out_host
         # eager fallback (CPU tests / enforce_eager): same semantics
@@ -859,6 +1017,25 @@ class ModelRunner:
         ctx = meta.context_lens
         out = torch.empty((k_steps, n), dtype=torch.int64)
         dev = input_ids.device
+        if processed:
+            # the graph variant's ops, step by step: one meaning on both paths
+            st = self.logit_state
+            reqs = batch.requests
+            lp_slots = torch.tensor(
+                [st.slot_of(r.request_id) for r in reqs],
+                dtype=torch.int32, device=dev,
+            )
+            presence, frequency, repetition, min_p = (
+                torch.tensor(
+                    [getattr(r.sampling_params, f) for r in reqs],
+                    dtype=torch.float32, device=dev,
+                )
+                for f in (
+                    "presence_penalty", "frequency_penalty",
+                    "repetition_penalty", "min_p",
+                )
+            )
+            sampled = True
         if sampled:
             reqs = batch.requests
             temps = torch.tensor(
@@ -899,7 +1076,22 @@ class ModelRunner:
             )
             hidden = self.model(input_ids, positions, self.kv_caches, meta_k)
             logits = self.model.compute_logits(hidden)
-            if sampled:
+            if processed:
+                _ops.logit_process(
+                    logits, st.counts, lp_slots, presence, frequency,
+                    repetition, st.bias_ids, st.bias_vals, st.bias_len,
+                    out=logits,
+                )
+                seeds = seed_base + (self._rng_step + k) * self._SEED_PRIME
+                rand = torch.empty(n, dtype=torch.int64, device=dev)
+                _ops.topk_topp_minp_sample_into(
+                    rand, logits, temps, top_p, top_k, min_p, seeds,
+                    generator=gen,
+                )
+                greedy = _ops.greedy_sample(logits)
+                tok = torch.where(gmask, greedy, rand)
+                _ops.token_count_add(st.counts, lp_slots, tok)
+            elif sampled:
                 seeds = seed_base + (self._rng_step + k) * self._SEED_PRIME
                 rand = _ops.random_sample(
                     logits, temps, top_p, top_k, seeds=seeds, generator=gen

@@ -472,6 +472,163 @@ def topk_topp_sample_into(
     return out
 
 
+def _check_rows(name: str, t: torch.Tensor, dtype, n: int, device) -> None:
+    if (
+        t.dtype != dtype
+        or t.dim() != 1
+        or t.shape[0] != n
+        or not t.is_contiguous()
+        or t.device != device
+    ):
+        raise ValueError(
+            f"{name} must be a contiguous {dtype} [{n}] tensor on {device}, "
+            f"got {t.dtype} {tuple(t.shape)} on {t.device}"
+        )
+
+
+def topk_topp_minp_sample_into(
+    out: torch.Tensor,
+    logits: torch.Tensor,
+    temperatures: torch.Tensor,
+    top_p: torch.Tensor,
+    top_k: torch.Tensor,
+    min_p: torch.Tensor,
+    seeds: torch.Tensor,
+    generator: Optional[torch.Generator] = None,
+) -> torch.Tensor:
+    """``topk_topp_sample_into`` with a per-row min-p (fp32 [S], <= 0 off):
+    an element is also dropped when its probability under the untruncated
+    softmax(logits / T) is below ``min_p`` times the maximum's; the mask is
+    OR-ed with top-k and top-p and the row maximum always survives. Device
+    tensors only (runs under capture); CPU tensors take the sort reference,
+    which draws from ``generator`` instead of ``seeds``."""
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous [S, V] tensor")
+    s, dev = logits.shape[0], logits.device
+    _check_rows("out", out, torch.int64, s, dev)
+    _check_rows("temperatures", temperatures, torch.float32, s, dev)
+    _check_rows("top_p", top_p, torch.float32, s, dev)
+    _check_rows("top_k", top_k, torch.int32, s, dev)
+    _check_rows("min_p", min_p, torch.float32, s, dev)
+    _check_rows("seeds", seeds, torch.int64, s, dev)
+    if logits.is_cuda:
+        if logits.dtype != torch.bfloat16:
+            raise TypeError(f"logits must be bf16 on GPU, got {logits.dtype}")
+        _native("topk_topp_minp_sample").topk_topp_minp_sample(
+            out, logits, temperatures, top_p, top_k, min_p, seeds
+        )
+        return out
+    out.copy_(
+        torch_ref.topk_topp_minp_sample(
+            logits, temperatures, top_p, top_k, min_p, generator=generator
+        )
+    )
+    return out
+
+
+def logit_process(
+    logits: torch.Tensor,
+    counts: torch.Tensor,
+    row_slot: torch.Tensor,
+    presence: torch.Tensor,
+    frequency: torch.Tensor,
+    repetition: torch.Tensor,
+    bias_ids: torch.Tensor,
+    bias_vals: torch.Tensor,
+    bias_len: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Apply logit_bias and then the presence / frequency / repetition
+    penalties to logits [S, V], row s from slot ``row_slot[s]`` of the
+    per-request state (``counts`` int32 [slots, V], ``bias_ids`` int32 /
+    ``bias_vals`` fp32 [slots, max_bias] with ``bias_len`` int32 [slots]
+    valid entries, ids unique within a slot).
+
+    Per element: a bias entry gives ``x = bf16(float(x) + bias)``; then, if
+    the token's count is positive, ``v = float(x)``, ``v = v / rep if v > 0
+    else v * rep`` when ``rep != 1``, ``x = bf16(v - presence - frequency *
+    count)``. Elements with neither and rows whose slot is outside
+    [0, slots) (-1 marks rows without processors and graph padding) keep
+    their bits. ``out=logits`` works in place; the default allocates.
+    Device tensors only (runs under capture)."""
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous [S, V] tensor")
+    s, v = logits.shape
+    dev = logits.device
+    if (
+        counts.dtype != torch.int32
+        or counts.dim() != 2
+        or counts.shape[1] != v
+        or not counts.is_contiguous()
+        or counts.device != dev
+    ):
+        raise ValueError(
+            f"counts must be a contiguous int32 [slots, {v}] tensor on {dev}"
+        )
+    slots = counts.shape[0]
+    _check_rows("row_slot", row_slot, torch.int32, s, dev)
+    _check_rows("presence", presence, torch.float32, s, dev)
+    _check_rows("frequency", frequency, torch.float32, s, dev)
+    _check_rows("repetition", repetition, torch.float32, s, dev)
+    _check_rows("bias_len", bias_len, torch.int32, slots, dev)
+    if (
+        bias_ids.dtype != torch.int32
+        or bias_vals.dtype != torch.float32
+        or bias_ids.dim() != 2
+        or bias_ids.shape[0] != slots
+        or bias_vals.shape != bias_ids.shape
+        or not bias_ids.is_contiguous()
+        or not bias_vals.is_contiguous()
+        or bias_ids.device != dev
+        or bias_vals.device != dev
+    ):
+        raise ValueError(
+            "bias_ids (int32) and bias_vals (fp32) must be contiguous "
+            f"[{slots}, max_bias] tensors on {dev}"
+        )
+    if out is not None and out is not logits:
+        if (
+            out.shape != logits.shape
+            or out.dtype != logits.dtype
+            or out.device != dev
+            or not out.is_contiguous()
+        ):
+            raise ValueError("out must match logits in shape, dtype, device")
+    if not logits.is_cuda:
+        return torch_ref.logit_process(
+            logits, counts, row_slot, presence, frequency, repetition,
+            bias_ids, bias_vals, bias_len, out=out,
+        )
+    if logits.dtype != torch.bfloat16:
+        raise TypeError(f"logits must be bf16 on GPU, got {logits.dtype}")
+    if out is None:
+        out = torch.empty_like(logits)
+    _native("logit_process").logit_process(
+        out, logits, counts, row_slot, presence, frequency, repetition,
+        bias_ids, bias_vals, bias_len,
+    )
+    return out
+
+
+def token_count_add(
+    counts: torch.Tensor, slot: torch.Tensor, token: torch.Tensor
+) -> None:
+    """``counts[slot[j], token[j]] += 1`` for every j (int32 slots, int64
+    tokens, as the samplers return them). Pairs with a slot outside
+    [0, slots) or a token outside [0, V) are skipped; duplicates all count.
+    Device tensors only (runs under capture)."""
+    dev = counts.device
+    if counts.dtype != torch.int32 or counts.dim() != 2 or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 [slots, V] tensor")
+    n = slot.numel()
+    _check_rows("slot", slot, torch.int32, n, dev)
+    _check_rows("token", token, torch.int64, n, dev)
+    if counts.is_cuda:
+        _native("token_count_add").token_count_add(counts, slot, token)
+        return
+    torch_ref.token_count_add(counts, slot, token)
+
+
 def lora_shrink(
     x: torch.Tensor,
     a_stack: torch.Tensor,

@@ -52,6 +52,15 @@ hipError_t ks_gumbel_sample(void*, const void*, const void*, const void*,
 hipError_t ks_topk_topp_sample(void*, const void*, const void*, const void*,
                                const void*, const void*, int, int,
                                hipStream_t);
+hipError_t ks_topk_topp_minp_sample(void*, const void*, const void*,
+                                    const void*, const void*, const void*,
+                                    const void*, int, int, hipStream_t);
+hipError_t ks_logit_process(void*, const void*, const void*, const void*,
+                            const void*, const void*, const void*,
+                            const void*, const void*, const void*, int, int,
+                            int, int, hipStream_t);
+hipError_t ks_token_count_add(void*, const void*, const void*, int, int, int,
+                              hipStream_t);
 hipError_t ks_mfma_probe(void*, const void*, const void*, hipStream_t);
 hipError_t ks_skinny_gemm(void*, void*, const void*, const void*, int, int,
                           int, long, hipStream_t);
@@ -395,6 +404,102 @@ void topk_topp_sample(at::Tensor& out, at::Tensor& logits,
                                 logits.size(0), logits.size(1),
                                 current_stream()),
             "topk_topp_sample");
+}
+
+// 1-D contiguous GPU tensor of `n` elements of dtype `ty`
+#define CHECK_ROW_PARAM(t, ty, n)                                          \
+  TORCH_CHECK((t).scalar_type() == (ty) && (t).is_cuda() &&                \
+                  (t).dim() == 1 && (t).is_contiguous() &&                 \
+                  (t).size(0) == (n),                                      \
+              #t " must be a contiguous 1-D GPU tensor of " #ty " [" #n "]")
+
+void topk_topp_minp_sample(at::Tensor& out, at::Tensor& logits,
+                           at::Tensor& temperatures, at::Tensor& top_p,
+                           at::Tensor& top_k, at::Tensor& min_p,
+                           at::Tensor& seeds) {
+  CHECK_BF16_CONTIG(logits);
+  TORCH_CHECK(logits.dim() == 2, "logits must be [S, V]");
+  const int64_t S = logits.size(0);
+  CHECK_ROW_PARAM(out, at::kLong, S);
+  CHECK_ROW_PARAM(temperatures, at::kFloat, S);
+  CHECK_ROW_PARAM(top_p, at::kFloat, S);
+  CHECK_ROW_PARAM(top_k, at::kInt, S);
+  CHECK_ROW_PARAM(min_p, at::kFloat, S);
+  CHECK_ROW_PARAM(seeds, at::kLong, S);
+  check_hip(ks_topk_topp_minp_sample(
+                out.data_ptr(), logits.data_ptr(), temperatures.data_ptr(),
+                top_p.data_ptr(), top_k.data_ptr(), min_p.data_ptr(),
+                seeds.data_ptr(), (int)S, (int)logits.size(1),
+                current_stream()),
+            "topk_topp_minp_sample");
+}
+
+// counts [slots, V] int32, contiguous, on the GPU
+#define CHECK_TOKEN_COUNTS(t)                                              \
+  TORCH_CHECK((t).scalar_type() == at::kInt && (t).is_cuda() &&            \
+                  (t).dim() == 2 && (t).is_contiguous(),                   \
+              #t " must be a contiguous int32 [slots, V] GPU tensor")
+
+void logit_process(at::Tensor& out, at::Tensor& logits, at::Tensor& counts,
+                   at::Tensor& row_slot, at::Tensor& presence,
+                   at::Tensor& frequency, at::Tensor& repetition,
+                   at::Tensor& bias_ids, at::Tensor& bias_vals,
+                   at::Tensor& bias_len) {
+  // out [S, V] bf16 <- bias then penalties on logits, per row from the slot
+  // row_slot[s] of counts / bias_*; rows with a slot outside [0, slots) keep
+  // their bits. out may be logits itself (in place).
+  CHECK_BF16_CONTIG(logits);
+  CHECK_BF16_CONTIG(out);
+  TORCH_CHECK(logits.dim() == 2 && out.sizes() == logits.sizes(),
+              "logits and out must both be [S, V]");
+  const int64_t S = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(S <= 65535, "at most 65535 rows per call");
+  const int64_t nbytes = S * V * 2;
+  const char* lo = (const char*)logits.data_ptr();
+  const char* oo = (const char*)out.data_ptr();
+  TORCH_CHECK(oo == lo || oo + nbytes <= lo || lo + nbytes <= oo,
+              "out must be logits itself or not overlap it");
+  CHECK_TOKEN_COUNTS(counts);
+  TORCH_CHECK(counts.size(1) == V, "counts must be [slots, V]");
+  const int64_t slots = counts.size(0);
+  CHECK_ROW_PARAM(row_slot, at::kInt, S);
+  CHECK_ROW_PARAM(presence, at::kFloat, S);
+  CHECK_ROW_PARAM(frequency, at::kFloat, S);
+  CHECK_ROW_PARAM(repetition, at::kFloat, S);
+  TORCH_CHECK(bias_ids.scalar_type() == at::kInt && bias_ids.is_cuda() &&
+                  bias_ids.dim() == 2 && bias_ids.is_contiguous() &&
+                  bias_ids.size(0) == slots,
+              "bias_ids must be a contiguous int32 [slots, max_bias] GPU "
+              "tensor");
+  TORCH_CHECK(bias_vals.scalar_type() == at::kFloat && bias_vals.is_cuda() &&
+                  bias_vals.is_contiguous() &&
+                  bias_vals.sizes() == bias_ids.sizes(),
+              "bias_vals must be a contiguous f32 [slots, max_bias] GPU "
+              "tensor");
+  CHECK_ROW_PARAM(bias_len, at::kInt, slots);
+  check_hip(ks_logit_process(
+                out.data_ptr(), logits.data_ptr(), counts.data_ptr(),
+                row_slot.data_ptr(), presence.data_ptr(),
+                frequency.data_ptr(), repetition.data_ptr(),
+                bias_ids.data_ptr(), bias_vals.data_ptr(),
+                bias_len.data_ptr(), (int)S, (int)V, (int)slots,
+                (int)bias_ids.size(1), current_stream()),
+            "logit_process");
+}
+
+void token_count_add(at::Tensor& counts, at::Tensor& slot,
+                     at::Tensor& token) {
+  // counts[slot[j], token[j]] += 1; out-of-range pairs skipped
+  CHECK_TOKEN_COUNTS(counts);
+  const int64_t n = slot.numel();
+  CHECK_ROW_PARAM(slot, at::kInt, n);
+  CHECK_ROW_PARAM(token, at::kLong, n);
+  TORCH_CHECK(n < (int64_t)1 << 31 && counts.size(1) < (int64_t)1 << 31,
+              "too many pairs or vocab entries");
+  check_hip(ks_token_count_add(counts.data_ptr(), slot.data_ptr(),
+                               token.data_ptr(), (int)n, (int)counts.size(0),
+                               (int)counts.size(1), current_stream()),
+            "token_count_add");
 }
 
 void skinny_gemm(at::Tensor& out, at::Tensor& x, at::Tensor& w) {
@@ -753,6 +858,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gumbel_sample", &gumbel_sample, "Gumbel-max temperature sampling");
   m.def("topk_topp_sample", &topk_topp_sample,
         "fused top-k/top-p + Gumbel-max sampler (radix-histogram select)");
+  m.def("topk_topp_minp_sample", &topk_topp_minp_sample,
+        "fused top-k/top-p/min-p + Gumbel-max sampler");
+  m.def("logit_process", &logit_process,
+        "logit_bias + presence/frequency/repetition penalties per row slot");
+  m.def("token_count_add", &token_count_add,
+        "counts[slot[j], token[j]] += 1 (atomic; out-of-range pairs skipped)");
   m.def("skinny_gemm", &skinny_gemm, "decode GEMM (N<=256, MFMA streaming)");
   m.def("skinny_gemm_w8", &skinny_gemm_w8,
         "decode GEMM, fp8 e4m3 weights x bf16 activations (N<=256)");

@@ -118,12 +118,20 @@ __device__ __forceinline__ unsigned int bf16_sort_key(short bits) {
                        : (unsigned int)(u | 0x8000u);
 }
 
+// MINP adds the min-p rule to the final pass: an element is also dropped when
+// its probability under the UNTRUNCATED softmax(logit/T) is below min_p times
+// the maximum's, i.e. (l_i - m) / T < log(min_p). The mask is OR-ed with
+// top-k/top-p (torch_ref.random_sample's rule); min_p <= 0 disables it for
+// the row and the row maximum always survives. A template parameter, so the
+// plain sampler's per-element loop is unchanged.
+template <bool MINP>
 __global__ __launch_bounds__(256) void topk_topp_sample_kernel(
     long* __restrict__ out,            // [S]
     const short* __restrict__ logits,  // [S, V] bf16
     const float* __restrict__ temperatures,
     const float* __restrict__ top_p,  // [S] (>=1 disables)
     const int* __restrict__ top_k,    // [S] (<=0 disables)
+    const float* __restrict__ min_p,  // [S] (MINP; <=0 disables)
     const long* __restrict__ seeds,   // [S]
     const int V) {
   const int s = blockIdx.x;
@@ -246,11 +254,22 @@ __global__ __launch_bounds__(256) void topk_topp_sample_kernel(
   // would pick among them at random. Without noise the ties fall to the
   // lowest index, exactly as greedy_sample breaks them.
   const bool argmax_only = (k == 1);
+  bool use_mp = false;
+  float log_mp = 0.f;
+  if constexpr (MINP) {
+    const float mp = min_p[s];
+    use_mp = mp > 0.f;
+    // <= 0, so the maximum (distance 0) is never below the cut
+    log_mp = use_mp ? fminf(__logf(mp), 0.f) : 0.f;
+  }
   float best = -1e38f;
   int best_idx = 0;
   for (int i = tid; i < V; i += 256) {
     const short b = row[i];
     if (bf16_sort_key(b) < thr) continue;
+    if constexpr (MINP) {
+      if (use_mp && (bf16_bits_to_float(b) - m) * inv_t < log_mp) continue;
+    }
     const unsigned int h = hash2(seed, (unsigned int)i);
     const float u = ((float)h + 1.0f) * 2.3283064e-10f;
     const float val = bf16_bits_to_float(b) * inv_t -
@@ -308,10 +327,26 @@ hipError_t ks_topk_topp_sample(void* out, const void* logits,
                                const void* top_k, const void* seeds,
                                int num_seqs, int vocab, hipStream_t stream) {
   if (num_seqs == 0) return hipSuccess;
-  hipLaunchKernelGGL(topk_topp_sample_kernel, dim3(num_seqs), dim3(256), 0,
-                     stream, (long*)out, (const short*)logits,
+  hipLaunchKernelGGL((topk_topp_sample_kernel<false>), dim3(num_seqs),
+                     dim3(256), 0, stream, (long*)out, (const short*)logits,
                      (const float*)temperatures, (const float*)top_p,
-                     (const int*)top_k, (const long*)seeds, vocab);
+                     (const int*)top_k, nullptr, (const long*)seeds, vocab);
+  HIP_CHECK_KERNEL();
+  return hipSuccess;
+}
+
+hipError_t ks_topk_topp_minp_sample(void* out, const void* logits,
+                                    const void* temperatures,
+                                    const void* top_p, const void* top_k,
+                                    const void* min_p, const void* seeds,
+                                    int num_seqs, int vocab,
+                                    hipStream_t stream) {
+  if (num_seqs == 0) return hipSuccess;
+  hipLaunchKernelGGL((topk_topp_sample_kernel<true>), dim3(num_seqs),
+                     dim3(256), 0, stream, (long*)out, (const short*)logits,
+                     (const float*)temperatures, (const float*)top_p,
+                     (const int*)top_k, (const float*)min_p,
+                     (const long*)seeds, vocab);
   HIP_CHECK_KERNEL();
   return hipSuccess;
 }

@@ -440,3 +440,82 @@ def kv_scatter_pages(kv_caches, block_ids, src: torch.Tensor) -> None:
     for layer, (k, v) in enumerate(kv_caches):
         _kv_pages_u8(k)[ids] = src[layer, 0]
         _kv_pages_u8(v)[ids] = src[layer, 1]
+
+
+def logit_process(
+    logits: torch.Tensor,      # [S, V]
+    counts: torch.Tensor,      # [slots, V] int32
+    row_slot: torch.Tensor,    # [S] int32
+    presence: torch.Tensor,    # [S] f32
+    frequency: torch.Tensor,   # [S] f32
+    repetition: torch.Tensor,  # [S] f32
+    bias_ids: torch.Tensor,    # [slots, max_bias] int32
+    bias_vals: torch.Tensor,   # [slots, max_bias] f32
+    bias_len: torch.Tensor,    # [slots] int32
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """logit_bias, then presence/frequency/repetition penalties, per row from
+    the slot ``row_slot[s]``; the steps (and the two roundings to the logits'
+    dtype) of ``Sampler._apply_penalties`` with int32 counts. Rows whose slot
+    is outside [0, slots) and elements with neither a bias nor a count keep
+    their bits. ``out`` may be ``logits`` itself."""
+    if out is None:
+        out = logits.clone()
+    elif out is not logits:
+        out.copy_(logits)
+    slots, vocab = counts.shape
+    for s in range(logits.shape[0]):
+        slot = int(row_slot[s])
+        if not 0 <= slot < slots:
+            continue
+        row = out[s]
+        nb = min(max(int(bias_len[slot]), 0), bias_ids.shape[1])
+        if nb:
+            ids = bias_ids[slot, :nb].long()
+            keep = (ids >= 0) & (ids < vocab)
+            ids = ids[keep]
+            row[ids] = (
+                row[ids].float() + bias_vals[slot, :nb][keep].float()
+            ).to(row.dtype)
+        cnt = counts[slot]
+        idx = (cnt > 0).nonzero().squeeze(-1)
+        if not idx.numel():
+            continue
+        vals = row[idx].float()
+        rep = float(repetition[s])
+        if rep != 1.0:
+            vals = torch.where(vals > 0, vals / rep, vals * rep)
+        vals = vals - float(presence[s]) - float(frequency[s]) * cnt[idx].float()
+        row[idx] = vals.to(row.dtype)
+    return out
+
+
+def token_count_add(
+    counts: torch.Tensor, slot: torch.Tensor, token: torch.Tensor
+) -> None:
+    """counts[slot[j], token[j]] += 1 for every j, duplicates included; pairs
+    with a slot outside [0, slots) or a token outside [0, V) are skipped."""
+    slots, vocab = counts.shape
+    sl = slot.long()
+    tk = token.long()
+    keep = (sl >= 0) & (sl < slots) & (tk >= 0) & (tk < vocab)
+    flat = sl[keep] * vocab + tk[keep]
+    counts.view(-1).index_add_(
+        0, flat, torch.ones_like(flat, dtype=counts.dtype)
+    )
+
+
+def topk_topp_minp_sample(
+    logits: torch.Tensor,
+    temperatures: torch.Tensor,
+    top_p: torch.Tensor,
+    top_k: torch.Tensor,
+    min_p: torch.Tensor,
+    generator: Optional[torch.Generator] = None,
+) -> torch.Tensor:
+    """``random_sample`` with per-row min-p, and the fused kernel's top_k == 1
+    contract: no noise, ties to the lowest index (as ``greedy_sample``)."""
+    out = random_sample(
+        logits, temperatures, top_p, top_k, generator=generator, min_p=min_p
+    )
+    return torch.where(top_k == 1, greedy_sample(logits), out)

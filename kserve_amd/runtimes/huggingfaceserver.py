@@ -115,6 +115,9 @@ def build_model(args):
                 max_num_seqs=getattr(args, "max_num_seqs", 256),
                 max_model_len=getattr(args, "max_model_len", 8192),
                 speculative_ngram=getattr(args, "speculative_ngram", 0),
+                logit_processor_slots=getattr(
+                    args, "logit_processor_slots", 0
+                ),
                 speculative_k=(
                     getattr(args, "num_speculative_tokens", 3)
                     if draft_cfg is not None
@@ -179,6 +182,11 @@ def build_parser():
     parser.add_argument("--kv-offload-bytes", dest="kv_offload_bytes", type=int, default=0)
     parser.add_argument("--kv-cache-dtype", dest="kv_cache_dtype", default="auto",
                         choices=["auto", "fp8"])
+    # in-graph logit processors: requests that set penalties, logit_bias or
+    # min_p keep multi-step decode windows while they hold one of N device
+    # state slots (N x vocab x 4 B; 64 slots at vocab 128256 = 33 MB). 0 = off
+    parser.add_argument("--logit-processor-slots",
+                        dest="logit_processor_slots", type=int, default=0)
     # weight-only fp8 (E4M3) or MXFP4 for the attention/MLP projections
     parser.add_argument("--quantization", dest="quantization", default=None,
                         choices=["none", "fp8", "mxfp4"])
