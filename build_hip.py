@@ -33,8 +33,7 @@ KERNEL_SOURCES = [
     "sampling.hip",
     "logit_process.hip",
     "skinny_gemm.hip",
-    "w8_gemm.hip",
-    "w4_gemm.hip",
+    "wq_gemm.hip",
     "lora.hip",
     "gemm8.hip",
     "mfma_probe.hip",
@@ -62,14 +61,16 @@ def build(force: bool = False) -> str:
     ]
     py_inc = sysconfig.get_paths()["include"]
 
-    common_h = os.path.join(CSRC, "common.h")
-    layouts_h = os.path.join(CSRC, "mfma_layouts.h")
+    # every kernel object depends on every header in csrc/
+    headers = [
+        os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")
+    ]
     objs = []
     for src in KERNEL_SOURCES:
         src_path = os.path.join(CSRC, src)
         obj = os.path.join(BUILD, src.replace(".hip", ".o"))
         objs.append(obj)
-        if force or newer(src_path, obj) or newer(common_h, obj) or newer(layouts_h, obj):
+        if force or any(newer(p, obj) for p in [src_path, *headers]):
             run([
                 HIPCC, "-c", src_path, "-o", obj,
                 f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",

@@ -307,6 +307,60 @@ def _w8_scratch(device, out_features: int, in_features: int) -> torch.Tensor:
     return buf
 
 
+def _linear_wq(
+    name: str,
+    x: torch.Tensor,
+    qweight: torch.Tensor,
+    scale: torch.Tensor,
+    bias: Optional[torch.Tensor],
+    *,
+    K: int,  # logical in_features of qweight
+    k_multiple: int,  # the kernel's K step
+    max_tokens: int,
+    gemm: str,  # binding names
+    dequant: str,
+    reference,  # CPU path
+) -> torch.Tensor:
+    """What linear_w8 and linear_w4 share. GPU: decode-sized batches run the
+    format's MFMA skinny GEMM (weights cross HBM once, as codes); everything
+    else (prefill, large batches, odd shapes) dequantizes into the shared
+    scratch, in row chunks, and runs hipBLASLt."""
+    if not x.is_cuda:
+        return reference(x, qweight, scale, bias)
+    C = _native(name)
+    import torch.nn.functional as F
+
+    M = qweight.shape[0]
+    if (
+        x.dim() == 2
+        and 0 < x.shape[0] <= max_tokens
+        and M % 64 == 0
+        and K % k_multiple == 0
+        and x.dtype == torch.bfloat16
+        and x.stride(1) == 1
+        and x.stride(0) % 8 == 0
+        and x.data_ptr() % 16 == 0
+    ):
+        out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
+        getattr(C, gemm)(out, x, qweight, scale)
+        if bias is not None:
+            out += bias
+        return out
+    if x.dtype != torch.bfloat16:
+        raise TypeError(f"{name} on GPU needs bf16 activations, got {x.dtype}")
+    buf = _w8_scratch(x.device, M, K)
+    rows = min(M, buf.numel() // K)
+    parts = []
+    for r0 in range(0, M, rows):
+        r1 = min(M, r0 + rows)
+        w = buf[: (r1 - r0) * K].view(r1 - r0, K)
+        getattr(C, dequant)(w, qweight[r0:r1], scale[r0:r1])
+        parts.append(
+            F.linear(x, w, None if bias is None else bias[r0:r1])
+        )
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+
+
 def linear_w8(
     x: torch.Tensor,
     qweight: torch.Tensor,
@@ -316,44 +370,13 @@ def linear_w8(
     """Weight-only fp8 linear: (x @ qweight^T) * scale (+ bias).
 
     qweight [M, K] float8_e4m3fn, scale [M] f32 (kserve_amd.ops.quant).
-    GPU: decode-sized batches run the fp8-weight MFMA skinny GEMM (weights
-    cross HBM once, as bytes); everything else (prefill, large batches, odd
-    shapes) dequantizes into the shared scratch and runs hipBLASLt.
     """
-    if not x.is_cuda:
-        return torch_ref.linear_w8(x, qweight, scale, bias)
-    C = _native("linear_w8")
-    import torch.nn.functional as F
-
-    M, K = qweight.shape
-    if (
-        x.dim() == 2
-        and 0 < x.shape[0] <= W8_MAX_TOKENS
-        and M % 64 == 0
-        and K % 64 == 0
-        and x.dtype == torch.bfloat16
-        and x.stride(1) == 1
-        and x.stride(0) % 8 == 0
-        and x.data_ptr() % 16 == 0
-    ):
-        out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
-        C.skinny_gemm_w8(out, x, qweight, scale)
-        if bias is not None:
-            out += bias
-        return out
-    if x.dtype != torch.bfloat16:
-        raise TypeError(f"linear_w8 on GPU needs bf16 activations, got {x.dtype}")
-    buf = _w8_scratch(x.device, M, K)
-    rows = min(M, buf.numel() // K)
-    parts = []
-    for r0 in range(0, M, rows):
-        r1 = min(M, r0 + rows)
-        w = buf[: (r1 - r0) * K].view(r1 - r0, K)
-        C.dequant_fp8_rows(w, qweight[r0:r1], scale[r0:r1])
-        parts.append(
-            F.linear(x, w, None if bias is None else bias[r0:r1])
-        )
-    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+    return _linear_wq(
+        "linear_w8", x, qweight, scale, bias,
+        K=qweight.shape[1], k_multiple=64, max_tokens=W8_MAX_TOKENS,
+        gemm="skinny_gemm_w8", dequant="dequant_fp8_rows",
+        reference=torch_ref.linear_w8,
+    )
 
 
 # Largest token batch ops.linear_w4 sends to the MXFP4-weight skinny GEMM;
@@ -375,45 +398,15 @@ def linear_w4(
     """Weight-only MXFP4 linear: x @ dequant(qweight, weight_scale)^T (+ bias).
 
     qweight uint8 [M, K/2], weight_scale uint8 [M, K/32]
-    (kserve_amd.ops.quant). GPU: decode-sized batches run the fp4-weight
-    MFMA skinny GEMM (weights cross HBM once, as 4.25 bits each);
-    everything else (prefill, large batches, odd shapes) dequantizes into
-    the scratch shared with linear_w8 and runs hipBLASLt.
+    (kserve_amd.ops.quant); the weights cross HBM as 4.25 bits each. The
+    dequant scratch is the one linear_w8 uses.
     """
-    if not x.is_cuda:
-        return torch_ref.linear_w4(x, qweight, weight_scale, bias)
-    C = _native("linear_w4")
-    import torch.nn.functional as F
-
-    M, K = qweight.shape[0], qweight.shape[1] * 2
-    if (
-        x.dim() == 2
-        and 0 < x.shape[0] <= W4_MAX_TOKENS
-        and M % 64 == 0
-        and K % 128 == 0
-        and x.dtype == torch.bfloat16
-        and x.stride(1) == 1
-        and x.stride(0) % 8 == 0
-        and x.data_ptr() % 16 == 0
-    ):
-        out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
-        C.skinny_gemm_w4(out, x, qweight, weight_scale)
-        if bias is not None:
-            out += bias
-        return out
-    if x.dtype != torch.bfloat16:
-        raise TypeError(f"linear_w4 on GPU needs bf16 activations, got {x.dtype}")
-    buf = _w8_scratch(x.device, M, K)
-    rows = min(M, buf.numel() // K)
-    parts = []
-    for r0 in range(0, M, rows):
-        r1 = min(M, r0 + rows)
-        w = buf[: (r1 - r0) * K].view(r1 - r0, K)
-        C.dequant_mxfp4_rows(w, qweight[r0:r1], weight_scale[r0:r1])
-        parts.append(
-            F.linear(x, w, None if bias is None else bias[r0:r1])
-        )
-    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+    return _linear_wq(
+        "linear_w4", x, qweight, weight_scale, bias,
+        K=qweight.shape[1] * 2, k_multiple=128, max_tokens=W4_MAX_TOKENS,
+        gemm="skinny_gemm_w4", dequant="dequant_mxfp4_rows",
+        reference=torch_ref.linear_w4,
+    )
 
 
 def layer_norm(x, weight, bias, eps: float):

@@ -66,10 +66,9 @@ hipError_t ks_skinny_gemm(void*, void*, const void*, const void*, int, int,
                           int, long, hipStream_t);
 hipError_t ks_gemm8(void*, const void*, const void*, int, int, int, int,
                     hipStream_t);
-int ks_skinny_gemm_w8_nsplit(int, int);
+int ks_skinny_nsplit(int, int, int);
 hipError_t ks_skinny_gemm_w8(void*, void*, const void*, const void*,
                              const void*, int, int, int, long, hipStream_t);
-int ks_skinny_gemm_w4_nsplit(int, int);
 hipError_t ks_skinny_gemm_w4(void*, void*, const void*, const void*,
                              const void*, int, int, int, long, hipStream_t);
 hipError_t ks_dequant_mxfp4_rows(void*, const void*, const void*, long, int,
@@ -502,6 +501,17 @@ void token_count_add(at::Tensor& counts, at::Tensor& slot,
             "token_count_add");
 }
 
+// bf16 partials for the kernel's K-split (each a full-precision-accumulated
+// K/nsplit dot), sized by the policy the launchers use; undefined when the
+// shape is not split. BK is the kernel's K step.
+at::Tensor split_k_workspace(const at::Tensor& x, int N, int M, int K,
+                             int BK) {
+  const int nsplit = ks_skinny_nsplit(M, K, BK);
+  if (nsplit <= 1) return at::Tensor();
+  return at::empty({(long)nsplit * N * M},
+                   at::TensorOptions().dtype(at::kBFloat16).device(x.device()));
+}
+
 void skinny_gemm(at::Tensor& out, at::Tensor& x, at::Tensor& w) {
   // out [N, M] bf16 = x [N, K] @ w [M, K]^T  (decode shapes, N <= 256)
   CHECK_BF16_CONTIG(out);
@@ -513,21 +523,10 @@ void skinny_gemm(at::Tensor& out, at::Tensor& x, at::Tensor& w) {
   int K = x.size(1);
   int M = w.size(0);
   TORCH_CHECK(w.size(1) == K, "shape mismatch");
-  at::Tensor ws;
-  void* wsp = nullptr;
-  // mirror the kernel's K-split decision to size the partials workspace
-  int nsplit = 1;
-  int feat_wgs = M / 64;
-  while (feat_wgs * nsplit < 768 && nsplit < 8 && (K / (nsplit * 2)) >= 64)
-    nsplit *= 2;
-  if (nsplit > 1) {
-    // bf16 partials (each a full-precision-accumulated K/nsplit dot)
-    ws = at::empty({(long)nsplit * N * M},
-                   at::TensorOptions().dtype(at::kBFloat16).device(x.device()));
-    wsp = ws.data_ptr();
-  }
-  check_hip(ks_skinny_gemm(out.data_ptr(), wsp, x.data_ptr(), w.data_ptr(),
-                           M, K, N, (long)x.stride(0), current_stream()),
+  at::Tensor ws = split_k_workspace(x, N, M, K, 64);
+  check_hip(ks_skinny_gemm(out.data_ptr(), ws.defined() ? ws.data_ptr() : nullptr,
+                           x.data_ptr(), w.data_ptr(), M, K, N,
+                           (long)x.stride(0), current_stream()),
             "skinny_gemm");
 }
 
@@ -540,35 +539,37 @@ void skinny_gemm(at::Tensor& out, at::Tensor& x, at::Tensor& w) {
                   (scale).numel() == (q).size(0),                         \
               #scale " must be f32 [out_features] on GPU")
 
-void skinny_gemm_w8(at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
-                    at::Tensor& scale) {
-  // out [N, M] bf16 = (x [N, K] bf16 @ qweight [M, K]^T e4m3) * scale [M]
-  CHECK_BF16_CONTIG(out);
-  CHECK_FP8_WEIGHT(qweight, scale);
+// The weight-quantized decode GEMMs, after their own weight check: `gemm` is
+// ks_skinny_gemm_w8 or _w4, wK the K that qweight holds, BK the kernel's K
+// step, max_n its token limit.
+void skinny_gemm_wq(const char* op, decltype(&ks_skinny_gemm_w8) gemm,
+                    int64_t wK, int BK, int max_n, at::Tensor& out,
+                    at::Tensor& x, at::Tensor& qweight, at::Tensor& scale) {
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_cuda() &&
                   x.dim() == 2 && x.stride(1) == 1,
               "x must be bf16 row-dense");
   int N = x.size(0);
   int K = x.size(1);
   int M = qweight.size(0);
-  TORCH_CHECK(qweight.size(1) == K && out.dim() == 2 && out.size(0) == N &&
+  TORCH_CHECK(wK == K && out.dim() == 2 && out.size(0) == N &&
                   out.size(1) == M,
               "shape mismatch");
-  TORCH_CHECK(N >= 1 && N <= 256 && M % 64 == 0 && K % 64 == 0,
-              "skinny_gemm_w8 needs 1 <= N <= 256, M % 64 == 0, K % 64 == 0");
-  at::Tensor ws;
-  void* wsp = nullptr;
-  const int nsplit = ks_skinny_gemm_w8_nsplit(M, K);
-  if (nsplit > 1) {
-    // bf16 partials (each a full-precision-accumulated K/nsplit dot)
-    ws = at::empty({(long)nsplit * N * M},
-                   at::TensorOptions().dtype(at::kBFloat16).device(x.device()));
-    wsp = ws.data_ptr();
-  }
-  check_hip(ks_skinny_gemm_w8(out.data_ptr(), wsp, x.data_ptr(),
-                              qweight.data_ptr(), scale.data_ptr(), M, K, N,
-                              (long)x.stride(0), current_stream()),
-            "skinny_gemm_w8");
+  TORCH_CHECK(N >= 1 && N <= max_n && M % 64 == 0 && K % BK == 0, op,
+              " needs 1 <= N <= ", max_n, ", M % 64 == 0, K % ", BK, " == 0");
+  at::Tensor ws = split_k_workspace(x, N, M, K, BK);
+  check_hip(gemm(out.data_ptr(), ws.defined() ? ws.data_ptr() : nullptr,
+                 x.data_ptr(), qweight.data_ptr(), scale.data_ptr(), M, K, N,
+                 (long)x.stride(0), current_stream()),
+            op);
+}
+
+void skinny_gemm_w8(at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
+                    at::Tensor& scale) {
+  // out [N, M] bf16 = (x [N, K] bf16 @ qweight [M, K]^T e4m3) * scale [M]
+  CHECK_BF16_CONTIG(out);
+  CHECK_FP8_WEIGHT(qweight, scale);
+  skinny_gemm_wq("skinny_gemm_w8", ks_skinny_gemm_w8, qweight.size(1), 64,
+                 256, out, x, qweight, scale);
 }
 
 void dequant_fp8_rows(at::Tensor& out, at::Tensor& qweight,
@@ -603,30 +604,8 @@ void skinny_gemm_w4(at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
   // out [N, M] bf16 = x [N, K] bf16 @ dequant(qweight [M, K/2], scale)^T
   CHECK_BF16_CONTIG(out);
   CHECK_MXFP4_WEIGHT(qweight, scale);
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_cuda() &&
-                  x.dim() == 2 && x.stride(1) == 1,
-              "x must be bf16 row-dense");
-  int N = x.size(0);
-  int K = x.size(1);
-  int M = qweight.size(0);
-  TORCH_CHECK(qweight.size(1) * 2 == K && out.dim() == 2 &&
-                  out.size(0) == N && out.size(1) == M,
-              "shape mismatch");
-  TORCH_CHECK(N >= 1 && N <= 128 && M % 64 == 0 && K % 128 == 0,
-              "skinny_gemm_w4 needs 1 <= N <= 128, M % 64 == 0, K % 128 == 0");
-  at::Tensor ws;
-  void* wsp = nullptr;
-  const int nsplit = ks_skinny_gemm_w4_nsplit(M, K);
-  if (nsplit > 1) {
-    // bf16 partials (each a full-precision-accumulated K/nsplit dot)
-    ws = at::empty({(long)nsplit * N * M},
-                   at::TensorOptions().dtype(at::kBFloat16).device(x.device()));
-    wsp = ws.data_ptr();
-  }
-  check_hip(ks_skinny_gemm_w4(out.data_ptr(), wsp, x.data_ptr(),
-                              qweight.data_ptr(), scale.data_ptr(), M, K, N,
-                              (long)x.stride(0), current_stream()),
-            "skinny_gemm_w4");
+  skinny_gemm_wq("skinny_gemm_w4", ks_skinny_gemm_w4, qweight.size(1) * 2,
+                 128, 128, out, x, qweight, scale);
 }
 
 void dequant_mxfp4_rows(at::Tensor& out, at::Tensor& qweight,

@@ -16,6 +16,7 @@
 // RMW contention).
 #include "common.h"
 #include "mfma_layouts.h"
+#include "skinny_shared.h"
 
 namespace {
 
@@ -179,16 +180,29 @@ void launch_nt(short* out, short* ws, const short* x, const short* w, int M,
 
 }  // namespace
 
+extern "C" int ks_skinny_nsplit(int M, int K, int BK) {
+  const int feat_wgs = M / 64;
+  int nsplit = 1;
+  while (feat_wgs * nsplit < 768 && nsplit < 8 && (K / (nsplit * 2)) >= BK)
+    nsplit *= 2;
+  return nsplit;
+}
+
+hipError_t ks_reduce_bf16_partials(short* out, const short* ws, long nm,
+                                   int nsplit, hipStream_t stream) {
+  hipLaunchKernelGGL(reduce_ws_kernel, dim3(2048), dim3(256), 0, stream, out,
+                     ws, nm, nsplit);
+  HIP_CHECK_KERNEL();
+  return hipSuccess;
+}
+
 extern "C" hipError_t ks_skinny_gemm(void* out, void* workspace,
                                      const void* x, const void* w, int M,
                                      int K, int N, long x_row_stride,
                                      hipStream_t stream) {
   if (M % 64 != 0 || K % BK != 0 || N > 256) return hipErrorInvalidValue;
-  const int feat_wgs = M / 64;
   // fill the chip (G11): aim for >= 768 workgroups via K-splits
-  int nsplit = 1;
-  while (feat_wgs * nsplit < 768 && nsplit < 8 && (K / (nsplit * 2)) >= BK)
-    nsplit *= 2;
+  const int nsplit = ks_skinny_nsplit(M, K, BK);
   if (nsplit > 1 && workspace == nullptr) return hipErrorInvalidValue;
   int k_per_split = ((K / nsplit + BK - 1) / BK) * BK;
   const int NT = (N + 15) / 16;
@@ -214,11 +228,8 @@ extern "C" hipError_t ks_skinny_gemm(void* out, void* workspace,
   }
 #undef CASE
   HIP_CHECK_KERNEL();
-  if (nsplit > 1) {
-    const long nm = (long)N * M;
-    hipLaunchKernelGGL(reduce_ws_kernel, dim3(2048), dim3(256), 0, stream,
-                       (short*)out, ws, nm, nsplit);
-    HIP_CHECK_KERNEL();
-  }
+  if (nsplit > 1)
+    return ks_reduce_bf16_partials((short*)out, ws, (long)N * M, nsplit,
+                                   stream);
   return hipSuccess;
 }

@@ -6,7 +6,7 @@ output channel (weight row); ``w ~= float(q) * scale[row]``. Activations
 stay bf16, so the only approximation is this one-time rounding of the
 weights: the fp8 -> bf16 convert in the kernel is exact (E4M3 fits bf16's
 mantissa) and the scale multiplies the fp32 accumulator after the K
-reduction (``torch_ref.linear_w8`` / ``w8_gemm.hip``).
+reduction (``torch_ref.linear_w8`` / ``wq_gemm.hip``).
 
 MXFP4 format (OCP microscaling), for a weight ``w [M, K]``, ``K % 32 == 0``:
 
@@ -19,17 +19,19 @@ MXFP4 format (OCP microscaling), for a weight ``w [M, K]``, ``K % 32 == 0``:
 - ``w[m][k] ~= e2m1(code[m][k]) * 2^(weight_scale[m][k/32] - 127)``.
 
 The scale is a power of two, so applying it (in the kernel's convert,
-``w4_gemm.hip``, or in ``torch_ref.linear_w4``) is exact wherever the
+``wq_gemm.hip``, or in ``torch_ref.linear_w4``) is exact wherever the
 product is a normal bf16; as with fp8 the only approximation is the
 one-time rounding of the weights.
 
 The quantizers are plain torch: they run once at load, on whatever device
-the shard is on.
+the shard is on. ``WEIGHT_FORMATS`` at the end describes both formats to the
+parallel linear layers (storage shapes, shard -> codes, which op to call).
 """
 
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import Callable, Optional, Tuple
 
 import torch
 
@@ -170,3 +172,80 @@ def check_mxfp4_scale(scale: torch.Tensor, out_features: int,
     if bool((scale == E8M0_NAN).any()):
         raise ValueError(f"{name} holds the E8M0 NaN code 255")
     return scale
+
+
+# ------------------------------------------- what a layer needs to know --
+
+
+def _fp8_shard(w: torch.Tensor, scale: Optional[torch.Tensor], dev):
+    if w.dtype == FP8_DTYPE:
+        if scale is None:
+            raise ValueError("fp8 checkpoint weight without weight_scale")
+        return w.to(dev), scale.float().to(dev)
+    if w.dtype == torch.uint8:
+        raise ValueError(
+            "an mxfp4 checkpoint cannot be loaded with quantization='fp8'"
+        )
+    return quantize_fp8_per_channel(w.to(dev))
+
+
+def _mxfp4_shard(w: torch.Tensor, scale: Optional[torch.Tensor], dev):
+    if w.dtype == torch.uint8:
+        if scale is None:
+            raise ValueError("mxfp4 checkpoint weight without weight_scale")
+        scale = check_mxfp4_scale(scale, w.shape[0], w.shape[1] * 2)
+        return w.to(dev), scale.to(dev)
+    if w.dtype == FP8_DTYPE:
+        raise ValueError(
+            "an fp8 checkpoint cannot be loaded with quantization='mxfp4'"
+        )
+    return quantize_mxfp4(w.to(dev))
+
+
+@dataclass(frozen=True)
+class WeightFormat:
+    """How a linear layer stores and runs one quantized format: ``qweight``
+    is ``code_dtype [out, in / per_byte]``; ``weight_scale`` is
+    ``scale_dtype [out]``, or ``[out, in / block]`` for a block format."""
+
+    name: str  # the ``quantization=`` value
+    code_dtype: torch.dtype
+    scale_dtype: torch.dtype
+    per_byte: int  # input features per qweight element
+    block: Optional[int]  # input features per scale; None: one per row
+    linear: str  # the ``kserve_amd.ops`` function that applies it
+    # (already-sliced shard, its checkpoint scale slice or None, device) ->
+    # (codes, scale) on device. A bf16/f32 shard is quantized here, after
+    # slicing, so scales are per rank; a pre-quantized one is checked and
+    # moved; the other format's codes are refused.
+    shard_to_codes: Callable
+
+    def storage_shapes(self, out_features: int, in_features: int):
+        """Shapes of (qweight, weight_scale) for a logical [out, in]."""
+        if self.block is None:
+            return (out_features, in_features // self.per_byte), (out_features,)
+        if in_features % self.block != 0:
+            raise ValueError(
+                f"{self.name} needs the per-rank in_features ({in_features}) "
+                f"to be a multiple of {self.block}"
+            )
+        return (
+            (out_features, in_features // self.per_byte),
+            (out_features, in_features // self.block),
+        )
+
+    def logical_shape(self, qweight: torch.Tensor) -> Tuple[int, int]:
+        """[out, in] of the weight a stored ``qweight`` stands for."""
+        return qweight.shape[0], qweight.shape[1] * self.per_byte
+
+
+WEIGHT_FORMATS = {
+    "fp8": WeightFormat(
+        "fp8", FP8_DTYPE, torch.float32, per_byte=1, block=None,
+        linear="linear_w8", shard_to_codes=_fp8_shard,
+    ),
+    "mxfp4": WeightFormat(
+        "mxfp4", torch.uint8, torch.uint8, per_byte=2, block=MXFP4_BLOCK,
+        linear="linear_w4", shard_to_codes=_mxfp4_shard,
+    ),
+}

@@ -42,31 +42,16 @@ class _QuantLinearBase(nn.Module):
         quantization: Optional[str],
     ) -> None:
         self.quantization = quant.check_quantization(quantization)
-        if self.quantization == "fp8":
+        # None, or the quant.WeightFormat of qweight/weight_scale
+        self.weight_format = quant.WEIGHT_FORMATS.get(self.quantization)
+        fmt = self.weight_format
+        if fmt is not None:
+            qshape, sshape = fmt.storage_shapes(out_local, in_local)
             self.qweight = nn.Parameter(
-                torch.empty(out_local, in_local, dtype=quant.FP8_DTYPE),
-                requires_grad=False,
+                torch.empty(qshape, dtype=fmt.code_dtype), requires_grad=False
             )
             self.weight_scale = nn.Parameter(
-                torch.empty(out_local, dtype=torch.float32),
-                requires_grad=False,
-            )
-        elif self.quantization == "mxfp4":
-            if in_local % quant.MXFP4_BLOCK != 0:
-                raise ValueError(
-                    f"mxfp4 needs the per-rank in_features ({in_local}) to "
-                    f"be a multiple of {quant.MXFP4_BLOCK}"
-                )
-            self.qweight = nn.Parameter(
-                torch.empty(out_local, in_local // 2, dtype=torch.uint8),
-                requires_grad=False,
-            )
-            self.weight_scale = nn.Parameter(
-                torch.empty(
-                    out_local, in_local // quant.MXFP4_BLOCK,
-                    dtype=torch.uint8,
-                ),
-                requires_grad=False,
+                torch.empty(sshape, dtype=fmt.scale_dtype), requires_grad=False
             )
         else:
             self.weight = nn.Parameter(
@@ -74,58 +59,19 @@ class _QuantLinearBase(nn.Module):
                 requires_grad=False,
             )
 
-    def _to_fp8(self, w: torch.Tensor, scale: Optional[torch.Tensor]):
-        """One already-sliced shard -> (codes, per-channel scale) on the
-        layer's device. ``scale`` is the matching slice of a pre-quantized
-        checkpoint's per-channel scale (None for a bf16/f32 shard, which is
-        quantized here, after slicing, so scales are per rank)."""
-        dev = self.qweight.device
-        if w.dtype == quant.FP8_DTYPE:
-            if scale is None:
-                raise ValueError("fp8 checkpoint weight without weight_scale")
-            return w.to(dev), scale.float().to(dev)
-        if w.dtype == torch.uint8:
-            raise ValueError(
-                "an mxfp4 checkpoint cannot be loaded with quantization='fp8'"
-            )
-        return quant.quantize_fp8_per_channel(w.to(dev))
-
-    def _to_mxfp4(self, w: torch.Tensor, scale: Optional[torch.Tensor]):
-        """One already-sliced shard -> (packed codes, E8M0 block scales) on
-        the layer's device. ``scale`` is the matching [rows, in/32] slice of
-        a pre-quantized checkpoint (None for a bf16/f32 shard, which is
-        quantized here, after slicing)."""
-        dev = self.qweight.device
-        if w.dtype == torch.uint8:
-            if scale is None:
-                raise ValueError("mxfp4 checkpoint weight without weight_scale")
-            scale = quant.check_mxfp4_scale(scale, w.shape[0], w.shape[1] * 2)
-            return w.to(dev), scale.to(dev)
-        if w.dtype == quant.FP8_DTYPE:
-            raise ValueError(
-                "an fp8 checkpoint cannot be loaded with quantization='mxfp4'"
-            )
-        return quant.quantize_mxfp4(w.to(dev))
-
     def _store_weight(self, pieces, scales=None) -> None:
         """Store this rank's shard, given as row-blocks that are
-        concatenated along the output dim (fused QKV / gate+up)."""
+        concatenated along the output dim (fused QKV / gate+up). ``scales``
+        are the matching slices of a pre-quantized checkpoint's scales."""
         scales = scales or [None] * len(pieces)
-        if self.quantization == "fp8":
-            qs = [self._to_fp8(w, s) for w, s in zip(pieces, scales)]
+        fmt = self.weight_format
+        if fmt is not None:
+            dev = self.qweight.device
+            qs = [fmt.shard_to_codes(w, s, dev) for w, s in zip(pieces, scales)]
             self.qweight.data.copy_(torch.cat([q for q, _ in qs], dim=0))
             self.weight_scale.data.copy_(torch.cat([s for _, s in qs], dim=0))
-            ops.reserve_w8_scratch(self.qweight.device, *self.qweight.shape)
-            return
-        if self.quantization == "mxfp4":
-            qs = [self._to_mxfp4(w, s) for w, s in zip(pieces, scales)]
-            self.qweight.data.copy_(torch.cat([q for q, _ in qs], dim=0))
-            self.weight_scale.data.copy_(torch.cat([s for _, s in qs], dim=0))
-            # the scratch is shared with fp8 and sized in bf16 elements
-            ops.reserve_w8_scratch(
-                self.qweight.device, self.qweight.shape[0],
-                self.qweight.shape[1] * 2,
-            )
+            # one scratch for every format, sized in bf16 elements
+            ops.reserve_w8_scratch(dev, *fmt.logical_shape(self.qweight))
             return
         dt = self.weight.dtype
 
@@ -148,24 +94,28 @@ class _QuantLinearBase(nn.Module):
     def random_init_weight(self, std: float, generator) -> None:
         """normal_ does not exist for fp8 or packed fp4 codes: draw a
         temporary in bf16 on the layer's device and quantize it."""
-        if self.quantization is not None:
-            shape = tuple(self.qweight.shape)
-            if self.quantization == "mxfp4":
-                shape = (shape[0], shape[1] * 2)
+        if self.weight_format is not None:
             tmp = torch.empty(
-                shape, dtype=torch.bfloat16,
-                device=self.qweight.device,
+                self.weight_format.logical_shape(self.qweight),
+                dtype=torch.bfloat16, device=self.qweight.device,
             ).normal_(0.0, std, generator=generator)
             self._store_weight([tmp])
         else:
             self.weight.normal_(0.0, std, generator=generator)
 
-    def _linear(self, x: torch.Tensor, bias: Optional[torch.Tensor] = None):
-        if self.quantization == "fp8":
-            return ops.linear_w8(x, self.qweight, self.weight_scale, bias)
-        if self.quantization == "mxfp4":
-            return ops.linear_w4(x, self.qweight, self.weight_scale, bias)
-        return ops.linear(x, self.weight, bias)
+    def _linear(
+        self, x: torch.Tensor, bias: Optional[torch.Tensor] = None,
+        rows: Optional[slice] = None,
+    ):
+        """x @ W^T (+ bias), or x @ W[rows]^T; codes and their scales are
+        sliced together."""
+        pick = (lambda t: t) if rows is None else (lambda t: t[rows])
+        fmt = self.weight_format
+        if fmt is not None:
+            return getattr(ops, fmt.linear)(
+                x, pick(self.qweight), pick(self.weight_scale), bias
+            )
+        return ops.linear(x, pick(self.weight), bias)
 
 
 class ColumnParallelLinear(_QuantLinearBase):
@@ -359,17 +309,7 @@ class RowParallelLinear(_QuantLinearBase):
                 rows = slice(c * step, (c + 1) * step)
                 if c * step >= self.out_features:
                     break
-                if self.quantization == "fp8":
-                    # codes and their scales are sliced together
-                    yc = ops.linear_w8(
-                        x, self.qweight[rows], self.weight_scale[rows]
-                    )
-                elif self.quantization == "mxfp4":
-                    yc = ops.linear_w4(
-                        x, self.qweight[rows], self.weight_scale[rows]
-                    )
-                else:
-                    yc = ops.linear(x, self.weight[rows])
+                yc = self._linear(x, rows=rows)
                 works.append(comm.tp_all_reduce_async(yc))
                 parts.append(yc)
             for w in works:

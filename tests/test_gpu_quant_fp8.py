@@ -4,6 +4,8 @@ dequantizer, ops.linear_w8 dispatch and the engine with quantization="fp8".
 Every shape is the smallest that reaches its code path (see the table in
 test_w8_gemm_matches_reference)."""
 
+import functools
+
 import pytest
 import torch
 
@@ -31,6 +33,19 @@ def _finite_bytes(shape, gen):
 # -- 1: every byte code converts exactly -------------------------------------
 
 
+def _all_codes_weight(M, K, row_step=None):
+    """byte[m][k] = (m * row_step + k) % 256 (row_step = K: the bytes count
+    up through the rows) with the two NaN codes replaced by 0, and
+    power-of-two scales 2^-12..2^3, so that code x scale is exact in bf16."""
+    m = torch.arange(M, dtype=torch.int32)[:, None]
+    k = torch.arange(K, dtype=torch.int32)[None, :]
+    codes = (m * (K if row_step is None else row_step) + k) % 256
+    codes[(codes == 0x7F) | (codes == 0xFF)] = 0
+    assert len(torch.unique(codes)) == 254  # all finite codes present
+    scale = torch.pow(2.0, (torch.arange(M) % 16 - 12).float())
+    return codes.to(torch.uint8).view(FP8), scale
+
+
 def test_every_code_converts_exactly(dev):
     """x = I: out[n][m] must be q[m][n] * scale[m] exactly. Catches a wrong
     nibble/half in the packed convert, a wrong scale<->feature mapping and
@@ -39,17 +54,58 @@ def test_every_code_converts_exactly(dev):
     import kserve_amd_C
 
     N, K, M = 64, 64, 256
-    codes = (torch.arange(M * K, dtype=torch.int32) % 256).reshape(M, K)
-    codes[(codes == 0x7F) | (codes == 0xFF)] = 0
-    assert len(torch.unique(codes)) == 254  # all finite codes present
-    q = codes.to(torch.uint8).view(FP8).to(dev)
-    scale = torch.pow(2.0, (torch.arange(M) % 16 - 12).float()).to(dev)
+    q, scale = _all_codes_weight(M, K)
+    q, scale = q.to(dev), scale.to(dev)
     x = torch.eye(N, K, dtype=torch.bfloat16, device=dev)
     out = torch.empty(N, M, dtype=torch.bfloat16, device=dev)
     kserve_amd_C.skinny_gemm_w8(out, x, q, scale)
     torch.cuda.synchronize()
     want = (q.float() * scale[:, None]).t()  # [n][m]
     assert torch.equal(out.float(), want)
+
+
+_EXACT_M = 64  # one feature workgroup: the policy splits K 8 ways
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_weight(K):
+    """(q, scale, want [M, K] f32) on the CPU, shared by the cases of a K.
+    code x 2^e has at most 4 significant bits, so want is exact in bf16."""
+    q, scale = _all_codes_weight(_EXACT_M, K, row_step=37)
+    want = q.float() * scale[:, None]
+    assert torch.equal(want.bfloat16().float(), want)
+    return q, scale, want
+
+
+@pytest.mark.parametrize(
+    "NT,steps",
+    # every NT the launcher can select, at 3 steps per split: once round
+    # the pipelined loop, then the single-step tail
+    [(nt, 3) for nt in (1, 2, 3, 4, 5, 6, 8, 12, 16)]
+    # 2: no loop + the two-step tail; 4: loop + the two-step tail
+    + [(3, 2), (3, 4)],
+)
+def test_every_instantiation_is_exact(dev, NT, steps):
+    """One-hot x selects N = 16 NT - 3 consecutive columns (a ragged last
+    token tile: the row clamp): out[n][m] must be q[m][off + n] * scale[m]
+    exactly, for windows that cover all of K. M = 64 and K = 8 * steps * 64
+    make every launch the 8-way split kernel plus the reduce; all partials
+    but one are zero, so the sum is exact too."""
+    import kserve_amd_C
+
+    N, M, K = 16 * NT - 3, _EXACT_M, 8 * steps * 64
+    q, scale, want = _exact_weight(K)
+    qd, sd, want = q.to(dev), scale.to(dev), want.to(dev)
+    x = torch.zeros(N, K, dtype=torch.bfloat16, device=dev)
+    rows = torch.arange(N, device=dev)
+    for off in list(range(0, K - N, N)) + [K - N]:
+        x[rows, off + rows] = 1.0
+        out = torch.empty(N, M, dtype=torch.bfloat16, device=dev)
+        kserve_amd_C.skinny_gemm_w8(out, x, qd, sd)
+        x[rows, off + rows] = 0.0
+        assert torch.equal(
+            out.float(), want[:, off:off + N].t()
+        ), f"columns {off}..{off + N - 1}"
 
 
 # -- 2: numerics vs torch_ref.linear_w8 --------------------------------------

@@ -5,6 +5,8 @@ engine with quantization="mxfp4".
 Every shape is the smallest that reaches its code path (see the table in
 test_w4_gemm_matches_reference)."""
 
+import functools
+
 import pytest
 import torch
 
@@ -73,6 +75,51 @@ def test_every_code_converts_exactly(dev, K):
         assert torch.equal(
             out.float().cpu(), want[:, off:off + 128].t()
         ), f"columns {off}..{off + 127}"
+
+
+_EXACT_M = 64  # one feature workgroup: the policy splits K 8 ways
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_weight(K):
+    """(q, scale, want [M, K] f32) on the CPU, shared by the cases of a K"""
+    from kserve_amd.ops import quant
+
+    q, scale = _all_codes_weight(_EXACT_M, K)
+    want = quant.dequantize_mxfp4(q, scale)
+    assert torch.equal(want.bfloat16().float(), want)
+    return q, scale, want
+
+
+@pytest.mark.parametrize(
+    "NT,steps",
+    # every NT the launcher can select, at 3 steps per split: once round
+    # the pipelined loop, then the single-step tail
+    [(nt, 3) for nt in (1, 2, 3, 4, 5, 6, 8)]
+    # 2: no loop + the two-step tail; 4: loop + the two-step tail
+    + [(3, 2), (3, 4)],
+)
+def test_every_instantiation_is_exact(dev, NT, steps):
+    """One-hot x selects N = 16 NT - 3 consecutive columns (a ragged last
+    token tile: the row clamp): out[n][m] must be the dequantized
+    w[m][off + n] exactly, for windows that cover all of K. M = 64 and
+    K = 8 * steps * 128 make every launch the 8-way split kernel plus the
+    reduce; all partials but one are zero, so the sum is exact too."""
+    import kserve_amd_C
+
+    N, M, K = 16 * NT - 3, _EXACT_M, 8 * steps * 128
+    q, scale, want = _exact_weight(K)
+    qd, sd, want = q.to(dev), scale.to(dev), want.to(dev)
+    x = torch.zeros(N, K, dtype=torch.bfloat16, device=dev)
+    rows = torch.arange(N, device=dev)
+    for off in list(range(0, K - N, N)) + [K - N]:
+        x[rows, off + rows] = 1.0
+        out = torch.empty(N, M, dtype=torch.bfloat16, device=dev)
+        kserve_amd_C.skinny_gemm_w4(out, x, qd, sd)
+        x[rows, off + rows] = 0.0
+        assert torch.equal(
+            out.float(), want[:, off:off + N].t()
+        ), f"columns {off}..{off + N - 1}"
 
 
 # -- 2: numerics vs torch_ref.linear_w4 --------------------------------------

@@ -119,6 +119,46 @@ class TestDecodeAsm:
             assert counts["ds_write"] == 0, (name, counts)
 
 
+class TestQuantGemmAsm:
+    def test_every_instantiation_keeps_its_counted_pipeline(self, tmp_path):
+        """wq_gemm.hip, every Fmt x NT x SPLIT: the MFMAs and X stage loads
+        the design gives (prologue + two loop steps + one tail step issue
+        loads, those and the other tail step compute: 4 x NI and 5 x KK x NT),
+        and exactly three counted waits at NW = 1 W load + 1 scale byte
+        (MXFP4) + NI, i.e. nothing drains the prefetch inside the K loop."""
+        bodies = kernel_bodies(compile_to_asm(tmp_path, "wq_gemm"))
+        formats = {
+            # mangled trait name: (NTs, KK, NI(NT), loads besides X per step)
+            "3Fp8": ((1, 2, 3, 4, 5, 6, 8, 12, 16), 2, lambda nt: (nt + 1) // 2, 1),
+            "5Mxfp4": ((1, 2, 3, 4, 5, 6, 8), 4, lambda nt: nt, 2),
+        }
+        seen = 0
+        for fmt, (nts, kk, ni, others) in formats.items():
+            for nt in nts:
+                for split in (0, 1):
+                    tag = f"skinny_gemm_wq_kernelINS_{fmt}ELi{nt}ELb{split}EE"
+                    body = [b for n, b in bodies.items() if tag in n]
+                    assert len(body) == 1, f"{tag}: {len(body)} kernels"
+                    body = body[0]
+                    seen += 1
+                    waits = re.findall(r"s_waitcnt vmcnt\((\d+)\)", body)
+                    counts = {
+                        "mfma": len(re.findall(r"v_mfma_f32_16x16x32_bf16", body)),
+                        "glds": len(re.findall(r"global_load_lds_dwordx4", body)),
+                        "counted": [w for w in waits if w != "0"],
+                        "vmcnt0": waits.count("0"),
+                    }
+                    assert counts["mfma"] == 5 * kk * nt, (tag, counts)
+                    assert counts["glds"] == 4 * ni(nt), (tag, counts)
+                    assert counts["counted"] == [str(ni(nt) + others)] * 3, (
+                        tag, counts)
+                    if fmt == "5Mxfp4":  # fp8's epilogue waits for its scale
+                        assert counts["vmcnt0"] <= 3, (tag, counts)
+                    assert "scratch_" not in body, f"{tag} spilled"
+        n_gemm = sum("skinny_gemm_wq_kernel" in n for n in bodies)
+        assert n_gemm == seen, f"{n_gemm} instantiations, {seen} checked"
+
+
 class TestSamplerAsm:
     def test_topk_sampler_has_no_scratch(self, tmp_path):
         """The radix-select sampler must stay in registers/LDS (scratch

@@ -712,13 +712,14 @@ def test_lora_on_quantized_base_layer():
 
 
 def test_x_tile_swizzle_is_a_conflict_free_bijection():
-    """w4_gemm.hip's LDS image, recomputed here: a tile row is 16 chunks of
+    """wq_gemm.hip's LDS image for the Mxfp4 trait, recomputed here: a tile
+    row is 16 chunks of
     16 B (256 B, one LDS bank row), chunk kc of token row r sits at slot
     chunk_perm(kc) ^ (r & 15). (1) The staging side and the read side
     agree: every (row, kc) is written once and found again. (2) Each of
     ds_read_b128's four 16-lane groups ({0-3,12-15,20-27}, {4-11,16-19,
     28-31} and the same +32) touches 16 distinct slots for every kk, which
-    the fp8 kernel's perm and the plain XOR do not achieve on 256-B rows."""
+    the Fp8 trait's perm and the plain XOR do not achieve on 256-B rows."""
 
     def perm(kc):
         return kc ^ ((kc & 4) << 1)
