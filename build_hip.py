@@ -21,6 +21,11 @@ OUT_SO = os.path.join(REPO, "kserve_amd_C.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
+# Sources compiled with packed fp32 instructions (v_pk_*_f32) turned off;
+# new kernels go here.
+NO_PACKED_FP32 = {"moe.hip"}
+NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+
 KERNEL_SOURCES = [
     "rmsnorm.hip",
     "layernorm.hip",
@@ -35,6 +40,7 @@ KERNEL_SOURCES = [
     "skinny_gemm.hip",
     "wq_gemm.hip",
     "lora.hip",
+    "moe.hip",
     "gemm8.hip",
     "mfma_probe.hip",
 ]
@@ -75,6 +81,7 @@ def build(force: bool = False) -> str:
                 HIPCC, "-c", src_path, "-o", obj,
                 f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
                 "-ffast-math",
+                *(NO_PACKED_FP32_FLAGS if src in NO_PACKED_FP32 else []),
             ])
 
     bind_src = os.path.join(CSRC, "bindings.cpp")

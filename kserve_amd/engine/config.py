@@ -58,8 +58,20 @@ class ModelConfig:
     # "mxfp4" (OCP E2M1 codes + one E8M0 scale per 32 inputs, W4A16);
     # kserve_amd/ops/quant.py. lm_head and the embedding stay bf16.
     quantization: Optional[str] = None
+    # how MoE blocks run decode-sized batches: "dense" (every local expert on
+    # every token, two bmm) or "routed" (grouped HIP kernels that read only
+    # the routed experts, ops.moe_routed_mlp). The environment variable
+    # KS_MOE_KERNEL sets the default.
+    moe_kernel: str = field(
+        default_factory=lambda: os.environ.get("KS_MOE_KERNEL") or "dense"
+    )
 
     def __post_init__(self):
+        if self.moe_kernel not in ("dense", "routed"):
+            raise ValueError(
+                f"unknown moe_kernel {self.moe_kernel!r}; "
+                "supported: 'dense', 'routed'"
+            )
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_heads
         if self.quantization not in (None, "fp8", "mxfp4"):

@@ -212,12 +212,19 @@ class LLMEngine:
             if config.model.num_local_experts > 0:
                 from kserve_amd.models.llama import MixtralMoE
 
+                # the routed kernels capture as well; their buckets follow
+                # their own batch limit
+                limit = (
+                    MixtralMoE.ROUTED_MAX_TOKENS
+                    if config.model.moe_kernel == "routed"
+                    else MixtralMoE.DENSE_MAX_TOKENS
+                )
                 self.runner.capture_decode_graphs(
                     batch_sizes=[
                         b
                         for b in (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128,
                                   192, 256, 384)
-                        if b <= MixtralMoE.DENSE_MAX_TOKENS
+                        if b <= limit
                     ]
                 )
             else:

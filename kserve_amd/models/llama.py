@@ -191,6 +191,8 @@ class MixtralMoE(nn.Module):
         self.layer_idx = layer_idx
         self.num_experts = config.num_local_experts
         self.top_k = config.num_experts_per_tok
+        # "routed": decode-sized GPU bf16 batches run ops.moe_routed_mlp
+        self.moe_kernel = getattr(config, "moe_kernel", "dense")
         H, inter = config.hidden_size, config.intermediate_size
         # expert parallelism: experts are PARTITIONED across the group
         # (full-width weights per expert) instead of every expert being
@@ -291,6 +293,24 @@ class MixtralMoE(nn.Module):
             )
         return out
 
+    # largest batch the routed kernels take over from the dense path
+    # (profiles/moe_routed.md); never above ops.MOE_ROUTED_MAX_TOKENS
+    ROUTED_MAX_TOKENS = 384
+
+    def _use_routed(self, x: torch.Tensor) -> bool:
+        """moe_kernel="routed" applies to GPU bf16 batches within the
+        kernels' limits, eager or capturing; the rest keeps today's paths."""
+        return (
+            self.moe_kernel == "routed"
+            and x.is_cuda
+            and x.dtype == torch.bfloat16
+            and self.w_gate_up.dtype == torch.bfloat16
+            and x.shape[0] <= self.ROUTED_MAX_TOKENS
+            and ops.moe_routed_supported(
+                x.shape[0], self.top_k, x.shape[1], self.inter_local
+            )
+        )
+
     def forward(self, x: torch.Tensor, meta=None) -> torch.Tensor:
         T = x.shape[0]
         router_logits = torch.nn.functional.linear(x.float(), self.gate.float())
@@ -300,7 +320,11 @@ class MixtralMoE(nn.Module):
         capturing = (
             x.is_cuda and torch.cuda.is_current_stream_capturing()
         )
-        if capturing or T <= self.DENSE_MAX_TOKENS:
+        if self._use_routed(x):
+            out = ops.moe_routed_mlp(
+                x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo
+            )
+        elif capturing or T <= self.DENSE_MAX_TOKENS:
             out = self._forward_dense(x, topi, topw)
         else:
             out = self._forward_sparse(x, topi, topw)

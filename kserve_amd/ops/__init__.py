@@ -668,6 +668,65 @@ def lora_expand_add(
     )
 
 
+# limits of the routed MoE kernels (csrc/moe.hip; the binding checks them)
+MOE_ROUTED_MAX_TOKENS = 384
+MOE_ROUTED_MAX_PAIRS = 768
+MOE_ROUTED_MAX_TOPK = 8
+
+
+def moe_routed_supported(T: int, top_k: int, hidden: int, inter: int) -> bool:
+    """Shapes the routed MoE kernels take (dtype and device aside)."""
+    return (
+        1 <= T <= MOE_ROUTED_MAX_TOKENS
+        and 1 <= top_k <= MOE_ROUTED_MAX_TOPK
+        and T * top_k <= MOE_ROUTED_MAX_PAIRS
+        and hidden % 64 == 0
+        and inter > 0
+        and inter % 64 == 0
+    )
+
+
+def moe_routed_mlp(
+    x: torch.Tensor,
+    topi: torch.Tensor,
+    topw: torch.Tensor,
+    w_gate_up: torch.Tensor,
+    w_down: torch.Tensor,
+    expert_lo: int = 0,
+) -> torch.Tensor:
+    """Routed mixture-of-experts SwiGLU MLP for decode-sized batches.
+
+    x [T, H] bf16, topi [T, k] int64 global expert ids, topw [T, k] f32,
+    w_gate_up [E_local, 2I, H] (gate rows then up rows), w_down
+    [E_local, H, I]; returns [T, H]. Only routed experts are read; pairs
+    whose expert is outside [expert_lo, expert_lo + E_local) contribute
+    nothing. The routing stays on the device and every grid depends on shapes
+    only, so the call can be captured once and replayed with any routing.
+    Bit-identical from run to run, and a row's result does not depend on the
+    other rows of the batch."""
+    if x.is_cuda:
+        C = _native("moe_routed_mlp")
+        T, H = x.shape
+        P = T * topi.shape[1]
+        E, inter = w_gate_up.shape[0], w_down.shape[2]
+        dev = x.device
+        out = torch.empty_like(x)
+        offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        sorted_pair = torch.empty(P, dtype=torch.int32, device=dev)
+        act = torch.empty((P, inter), dtype=x.dtype, device=dev)
+        y = torch.empty(
+            (C.moe_nsplit(inter), P, H), dtype=torch.float32, device=dev
+        )
+        C.moe_routed_mlp(
+            out, x, topi, topw.float(), w_gate_up, w_down, int(expert_lo),
+            offsets, sorted_pair, act, y,
+        )
+        return out
+    return torch_ref.moe_routed_mlp(
+        x, topi, topw, w_gate_up, w_down, expert_lo
+    )
+
+
 # -- KV export / import (prefill-decode disaggregation) ----------------------
 
 # device table of the 2L cache base pointers (K0, V0, K1, V1, ...), built the

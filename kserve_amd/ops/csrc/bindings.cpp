@@ -80,6 +80,11 @@ hipError_t ks_lora_shrink(void*, const void*, const void*, const void*,
 hipError_t ks_lora_expand_add(void*, const void*, const void*, const void*,
                               const void*, const void*, int, int, int, int,
                               long, int, hipStream_t);
+int ks_moe_nsplit(int);
+hipError_t ks_moe_routed_mlp(void*, const void*, const void*, const void*,
+                             const void*, const void*, void*, void*, void*,
+                             void*, int, int, int, int, int, int,
+                             hipStream_t);
 hipError_t ks_kv_gather_pages(void*, const void*, const void*, int, int, long,
                               int, int, int, int, hipStream_t);
 hipError_t ks_kv_scatter_pages(const void*, const void*, const void*, int, int,
@@ -707,6 +712,67 @@ void lora_expand_add(at::Tensor& y, at::Tensor& tmp, at::Tensor& b_stack,
             "lora_expand_add");
 }
 
+int64_t moe_nsplit(int64_t inter) { return ks_moe_nsplit((int)inter); }
+
+void moe_routed_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+                    at::Tensor& topw, at::Tensor& w_gate_up,
+                    at::Tensor& w_down, int64_t expert_lo,
+                    at::Tensor& offsets, at::Tensor& sorted_pair,
+                    at::Tensor& act, at::Tensor& y) {
+  // out [T, H] bf16 <- routed SwiGLU experts of x [T, H]; topi [T, k] int64
+  // global expert ids, topw [T, k] f32, w_gate_up [E, 2I, H], w_down
+  // [E, H, I]; pairs whose expert is outside [expert_lo, expert_lo + E)
+  // contribute nothing. The rest are workspaces (ops.moe_routed_mlp).
+  CHECK_BF16_CONTIG(out);
+  CHECK_BF16_CONTIG(x);
+  CHECK_BF16_CONTIG(w_gate_up);
+  CHECK_BF16_CONTIG(w_down);
+  CHECK_BF16_CONTIG(act);
+  TORCH_CHECK(x.dim() == 2 && w_gate_up.dim() == 3 && w_down.dim() == 3 &&
+                  topi.dim() == 2,
+              "moe_routed_mlp: x [T, H], topi [T, k], w_gate_up [E, 2I, H], "
+              "w_down [E, H, I]");
+  const int64_t T = x.size(0), H = x.size(1), k = topi.size(1);
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  TORCH_CHECK(T >= 1 && T <= 384 && T * k <= 768,
+              "moe_routed_mlp needs 1 <= T <= 384 and T * k <= 768");
+  TORCH_CHECK(k >= 1 && k <= 8, "moe_routed_mlp needs top-k <= 8");
+  TORCH_CHECK(E >= 1 && E <= 256, "moe_routed_mlp needs <= 256 local experts");
+  TORCH_CHECK(H % 64 == 0 && I > 0 && I % 64 == 0,
+              "moe_routed_mlp needs H % 64 == 0 and I % 64 == 0");
+  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) == H &&
+                  w_down.size(0) == E && w_down.size(1) == H,
+              "moe_routed_mlp: expert weight shapes disagree");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == T && out.size(1) == H,
+              "out must be [T, H]");
+  TORCH_CHECK(topi.scalar_type() == at::kLong && topi.is_cuda() &&
+                  topi.is_contiguous() && topi.size(0) == T,
+              "topi must be a contiguous int64 [T, k] GPU tensor");
+  TORCH_CHECK(topw.scalar_type() == at::kFloat && topw.is_cuda() &&
+                  topw.is_contiguous() && topw.sizes() == topi.sizes(),
+              "topw must be a contiguous f32 [T, k] GPU tensor");
+  TORCH_CHECK(expert_lo >= 0 && expert_lo < (1 << 30),
+              "expert_lo out of range");
+  auto is_i32 = [](const at::Tensor& t, int64_t n) {
+    return t.scalar_type() == at::kInt && t.is_cuda() && t.is_contiguous() &&
+           t.numel() == n;
+  };
+  TORCH_CHECK(is_i32(offsets, E + 1) && is_i32(sorted_pair, T * k),
+              "offsets / sorted_pair must be int32 [E + 1] / [T * k]");
+  TORCH_CHECK(act.numel() == T * k * I, "act must be bf16 [T * k, I]");
+  TORCH_CHECK(y.scalar_type() == at::kFloat && y.is_cuda() &&
+                  y.is_contiguous() &&
+                  y.numel() == ks_moe_nsplit((int)I) * T * k * H,
+              "y must be f32 [moe_nsplit(I), T * k, H]");
+  check_hip(ks_moe_routed_mlp(out.data_ptr(), x.data_ptr(), topi.data_ptr(),
+                              topw.data_ptr(), w_gate_up.data_ptr(),
+                              w_down.data_ptr(), offsets.data_ptr(),
+                              sorted_pair.data_ptr(), act.data_ptr(),
+                              y.data_ptr(), (int)T, (int)k, (int)H, (int)I,
+                              (int)E, (int)expert_lo, current_stream()),
+            "moe_routed_mlp");
+}
+
 // Shared checks of the KV export/import ops. `caches` is K0, V0, K1, V1, ...
 // and `bases` the device table of their base pointers in the same order
 // (built once by the caller); returns the bytes of one page of one tensor.
@@ -859,6 +925,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("y"), pybind11::arg("tmp"), pybind11::arg("b_stack"),
         pybind11::arg("scale"), pybind11::arg("ranks"),
         pybind11::arg("slot_idx"), pybind11::arg("out_offset") = 0);
+  m.def("moe_nsplit", &moe_nsplit,
+        "K splits of the routed MoE down GEMM for an intermediate size");
+  m.def("moe_routed_mlp", &moe_routed_mlp,
+        "routed MoE SwiGLU MLP for decode batches (grouped MFMA GEMMs)");
   m.def("kv_gather_pages", &kv_gather_pages,
         "gather a request's KV pages of every layer into one buffer");
   m.def("kv_scatter_pages", &kv_scatter_pages,

@@ -400,6 +400,33 @@ def lora_expand_add(
     return y
 
 
+def moe_routed_mlp(
+    x: torch.Tensor,          # [T, H]
+    topi: torch.Tensor,       # [T, k] int64, global expert ids
+    topw: torch.Tensor,       # [T, k] routing weights
+    w_gate_up: torch.Tensor,  # [E_local, 2I, H] (gate rows, then up rows)
+    w_down: torch.Tensor,     # [E_local, H, I]
+    expert_lo: int = 0,
+) -> torch.Tensor:
+    """Routed MoE SwiGLU MLP, fp32 reference: out[t] = sum_j topw[t, j] *
+    down_e(silu(gate_e(x[t])) * up_e(x[t])) with e = topi[t, j] - expert_lo.
+    Pairs whose e is outside [0, E_local) contribute nothing (remote experts
+    under EP, or ids that name no expert). The activation is rounded to x's
+    dtype before the down projection, the output once at the end."""
+    E, inter = w_gate_up.shape[0], w_down.shape[2]
+    xf = x.float()
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    for le in range(E):
+        t_idx, j_idx = (topi == expert_lo + le).nonzero(as_tuple=True)
+        if t_idx.numel() == 0:
+            continue
+        gu = xf[t_idx] @ w_gate_up[le].float().t()
+        act = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
+        ye = act.to(x.dtype).float() @ w_down[le].float().t()
+        out.index_add_(0, t_idx, ye * topw[t_idx, j_idx].float().unsqueeze(1))
+    return out.to(x.dtype)
+
+
 def _kv_pages_u8(t: torch.Tensor) -> torch.Tensor:
     """Byte view [num_blocks, Hkv, block_size, D*itemsize] of a cache."""
     return t.view(torch.uint8)

@@ -65,6 +65,10 @@ def engine_model_config(args):
     quantization = getattr(args, "quantization", None)
     if quantization not in (None, "none"):
         model_cfg.quantization = quantization
+    # --moe-kernel dense|routed: how MoE blocks run decode-sized batches
+    moe_kernel = getattr(args, "moe_kernel", None)
+    if moe_kernel is not None:
+        model_cfg.moe_kernel = moe_kernel
     return model_cfg
 
 
@@ -190,6 +194,10 @@ def build_parser():
     # weight-only fp8 (E4M3) or MXFP4 for the attention/MLP projections
     parser.add_argument("--quantization", dest="quantization", default=None,
                         choices=["none", "fp8", "mxfp4"])
+    # MoE decode path: dense bmm over every expert, or the routed grouped
+    # HIP kernels (default: KS_MOE_KERNEL, else dense)
+    parser.add_argument("--moe-kernel", dest="moe_kernel", default=None,
+                        choices=["dense", "routed"])
     # LoRA adapter serving (reference: --enable-lora --lora-modules name=path)
     parser.add_argument("--speculative-draft-model",
                         dest="speculative_draft_model", default=None,

@@ -5,6 +5,7 @@ shape, to judge hipBLASLt (tuned/untuned) against the HBM roofline.
 Run on GPU: python tools/gemm_bench.py [--tune]
             python tools/gemm_bench.py --w8 [--out FILE.md]
             python tools/gemm_bench.py --w4 [--out FILE.md]
+            python tools/gemm_bench.py --moe [--out FILE.md]
 
 --w8 is the A/B behind ops.W8_MAX_TOKENS (profiles/w8_gemm.md): per
 Llama-3-8B projection shape and token batch it times, in one process and
@@ -15,6 +16,10 @@ threshold.
 --w4 is the same A/B behind ops.W4_MAX_TOKENS (profiles/w4_gemm.md), with
 the columns (a) ops.linear on bf16 weights, (b) the fp8-weight skinny GEMM,
 (c) the MXFP4-weight skinny GEMM and (d) MXFP4 dequant + hipBLASLt.
+
+--moe is the A/B behind MixtralMoE.ROUTED_MAX_TOKENS (profiles/
+moe_routed.md): one Mixtral-8x7B MoE layer per token batch, the routed
+grouped kernels (ops.moe_routed_mlp) against the dense-bmm path.
 """
 
 import argparse
@@ -30,8 +35,12 @@ parser.add_argument("--w8", action="store_true",
                     help="fp8-weight A/B table instead of the bf16 table")
 parser.add_argument("--w4", action="store_true",
                     help="MXFP4-weight A/B table instead of the bf16 table")
+parser.add_argument("--moe", action="store_true",
+                    help="routed MoE MLP against the dense-bmm path, one "
+                         "Mixtral-8x7B layer (profiles/moe_routed.md)")
 parser.add_argument("--out", default=None,
-                    help="--w8/--w4: also write the table as markdown here")
+                    help="--w8/--w4/--moe: also write the table as markdown "
+                         "here")
 args = parser.parse_args()
 
 if args.tune:
@@ -286,6 +295,113 @@ def bench_w4():
             f.write("\n".join(lines) + "\n" + tail + "\n")
 
 
+def bench_moe():
+    """One Mixtral-8x7B MoE layer (H 4096, I 14336, E 8, k 2), uniform
+    random routing: ops.moe_routed_mlp against MixtralMoE._forward_dense on
+    the same inputs, rounds interleaved, device-event timed, median and
+    spread of the rounds. Bytes are the weights of the experts the batch
+    routes to (what the routed path has to read), FLOPs those of the routed
+    pairs (2 * T*k * 3*H*I); the bound is the larger of bytes / 8 TB/s and
+    FLOPs / 2.5 PFLOP/s (MI355X HBM3E and dense bf16 MFMA peaks). The output
+    check is the allowance of tests/test_gpu_moe_routed.py, computed here
+    around the dense result."""
+    import statistics
+
+    from kserve_amd import ops
+    from kserve_amd.engine.config import ModelConfig
+    from kserve_amd.models.llama import MixtralMoE
+
+    H, I, E, k = 4096, 14336, 8, 2
+    PEAK_BW, PEAK_FLOPS = 8.0e12, 2.5e15
+    rounds = 5
+    cfg = ModelConfig.mixtral_8x7b()
+    with torch.device(dev):
+        moe = MixtralMoE(cfg, dtype=torch.bfloat16)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    moe.w_gate_up.data.normal_(0, H ** -0.5, generator=gen)
+    moe.w_down.data.normal_(0, I ** -0.5, generator=gen)
+
+    def timed(fn, iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(iters):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / iters * 1000
+
+    lines = [
+        "| T | experts routed | dense us | spread | routed us | spread "
+        "| dense/routed | routed TB/s | routed TFLOP/s | bound | % of bound "
+        "| max diff / allowance |",
+        "|---|---|---|---|---|---|---|---|---|---|---|---|",
+    ]
+    print(lines[0]); print(lines[1])
+    for T in (1, 4, 16, 64, 128, 256, 384):
+        x = torch.randn(T, H, dtype=torch.bfloat16, device=dev, generator=gen)
+        logits = torch.randn(T, E, device=dev, generator=gen)
+        topw, topi = torch.softmax(logits, -1).topk(k, -1)
+        topw = topw / topw.sum(-1, keepdim=True)
+
+        def fd():
+            return moe._forward_dense(x, topi, topw)
+
+        def fr():
+            return ops.moe_routed_mlp(
+                x, topi, topw, moe.w_gate_up, moe.w_down, 0
+            )
+
+        iters = max(args.iters // 2, 10)
+        res = {"d": [], "r": []}
+        for r in range(rounds + 1):  # round 0 is warm-up
+            for key, fn in (("d", fd), ("r", fr)):
+                t = timed(fn, iters)
+                if r:
+                    res[key].append(t)
+        d, rt = (statistics.median(res[key]) for key in "dr")
+        sd, sr = (
+            (max(res[key]) - min(res[key])) / statistics.median(res[key])
+            for key in "dr"
+        )
+        routed = int(topi.unique().numel())
+        wbytes = routed * 3 * H * I * 2
+        flops = 2 * T * k * 3 * H * I
+        t_bw, t_fl = wbytes / PEAK_BW * 1e6, flops / PEAK_FLOPS * 1e6
+        bound = "bytes" if t_bw >= t_fl else "FLOPs"
+        # allowance around the dense result (it is exact up to its own bf16
+        # roundings): |act| @ |w_down| per routed pair, in f32
+        ref = fd().float()
+        allow = torch.zeros_like(ref)
+        for e in range(E):
+            t_idx, j_idx = (topi == e).nonzero(as_tuple=True)
+            if t_idx.numel() == 0:
+                continue
+            act = ops.silu_and_mul(x[t_idx] @ moe.w_gate_up[e].t()).float()
+            allow.index_add_(
+                0, t_idx,
+                (act.abs() @ moe.w_down[e].float().abs().t())
+                * topw[t_idx, j_idx].unsqueeze(1),
+            )
+        allow = 2.0 ** -8 * ref.abs() + (2.0 ** -8 + (H + I) * 2.0 ** -23) * allow
+        ratio = ((fr().float() - ref).abs() / allow).max().item()
+        line = (
+            f"| {T} | {routed} | {d:.1f} | {sd:.1%} | {rt:.1f} | {sr:.1%} "
+            f"| {d / rt:.2f} | {wbytes / rt / 1e6:.2f} "
+            f"| {flops / rt / 1e6:.1f} | {bound} "
+            f"| {max(t_bw, t_fl) / rt:.0%} | {ratio:.3f} |"
+        )
+        print(line, flush=True)
+        lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if args.moe:
+    bench_moe()
+    sys.exit(0)
 if args.w8:
     bench_w8()
     sys.exit(0)
