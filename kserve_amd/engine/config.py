@@ -56,7 +56,11 @@ class ModelConfig:
     # weight-only quantization of the attention/MLP projections: None
     # (bf16), "fp8" (OCP E4M3 codes + per-channel f32 scales, W8A16) or
     # "mxfp4" (OCP E2M1 codes + one E8M0 scale per 32 inputs, W4A16);
-    # kserve_amd/ops/quant.py. lm_head and the embedding stay bf16.
+    # kserve_amd/ops/quant.py. lm_head, the embedding and the MoE router
+    # stay bf16. The stacked experts of a mixture-of-experts model are
+    # quantized too; that needs moe_kernel="routed" (the dense-bmm path has
+    # no quantized form) and per-rank hidden and intermediate sizes that
+    # are multiples of ops.MOE_ROUTED_K_STEP[quantization].
     quantization: Optional[str] = None
     # how MoE blocks run decode-sized batches: "dense" (every local expert on
     # every token, two bmm) or "routed" (grouped HIP kernels that read only

@@ -219,6 +219,15 @@ class LLMEngine:
                     if config.model.moe_kernel == "routed"
                     else MixtralMoE.DENSE_MAX_TOKENS
                 )
+                if config.model.quantization is not None:
+                    # quantized experts have no capturable path beside the
+                    # routed kernel, which takes at most MAX_PAIRS (T * k)
+                    # pairs; larger batches run eager
+                    limit = min(
+                        limit,
+                        ops.MOE_ROUTED_MAX_PAIRS
+                        // config.model.num_experts_per_tok,
+                    )
                 self.runner.capture_decode_graphs(
                     batch_sizes=[
                         b

@@ -217,38 +217,149 @@ class MixtralMoE(nn.Module):
             requires_grad=False,
         )
         # stacked per-expert weights: [E_local, 2*I_local, H] (gate|up) and
-        # [E_local, H, I_local]
+        # [E_local, H, I_local]. With config.quantization they hold the
+        # format's codes ([.., in / per_byte]) and w_*_scale their scales
+        # (quant.WeightFormat.storage_shapes per expert); no bf16 copy.
+        self.quantization = quant.check_quantization(
+            getattr(config, "quantization", None)
+        )
+        self.weight_format = fmt = quant.WEIGHT_FORMATS.get(self.quantization)
+        E, I_loc = self.experts_per_rank, self.inter_local
+        if fmt is None:
+            gu_shape, d_shape = (2 * I_loc, H), (H, I_loc)
+        else:
+            if self.moe_kernel != "routed":
+                raise ValueError(
+                    f"quantization={self.quantization!r} on a "
+                    "mixture-of-experts block needs moe_kernel='routed'"
+                )
+            step = ops.MOE_ROUTED_K_STEP[self.quantization]
+            if H % step != 0 or I_loc % step != 0:
+                # graph capture has no fallback for a shape the kernel
+                # cannot take, so refuse it here
+                raise ValueError(
+                    f"quantization={self.quantization!r} with "
+                    f"moe_kernel='routed' needs the per-rank hidden size "
+                    f"({H}) and expert intermediate size ({I_loc}) to be "
+                    f"multiples of {step}"
+                )
+            if self.top_k > ops.MOE_ROUTED_MAX_TOPK or E > 256:
+                raise ValueError(
+                    f"quantization={self.quantization!r} with "
+                    f"moe_kernel='routed' takes at most "
+                    f"{ops.MOE_ROUTED_MAX_TOPK} experts per token and 256 "
+                    f"experts per rank, got {self.top_k} and {E}"
+                )
+            gu_shape, gu_sshape = fmt.storage_shapes(2 * I_loc, H)
+            d_shape, d_sshape = fmt.storage_shapes(H, I_loc)
+            dtype = fmt.code_dtype
+            self.w_gate_up_scale = nn.Parameter(
+                torch.empty((E, *gu_sshape), dtype=fmt.scale_dtype),
+                requires_grad=False,
+            )
+            self.w_down_scale = nn.Parameter(
+                torch.empty((E, *d_sshape), dtype=fmt.scale_dtype),
+                requires_grad=False,
+            )
         self.w_gate_up = nn.Parameter(
-            torch.empty(
-                self.experts_per_rank, 2 * self.inter_local, H, dtype=dtype
-            ),
-            requires_grad=False,
+            torch.empty((E, *gu_shape), dtype=dtype), requires_grad=False
         )
         self.w_down = nn.Parameter(
-            torch.empty(
-                self.experts_per_rank, H, self.inter_local, dtype=dtype
-            ),
-            requires_grad=False,
+            torch.empty((E, *d_shape), dtype=dtype), requires_grad=False
         )
+
+    def _store_expert(self, local_e: int, gate, up, down) -> None:
+        """Store one expert's rank-local shards, each a (weight, checkpoint
+        scale slice or None) pair: quantized after slicing (scales are per
+        rank), or checked and copied when they already are this format's
+        codes; the other format's codes are refused (shard_to_codes)."""
+        fmt = self.weight_format
+        I_loc = self.inter_local
+        if fmt is None:
+            dt = self.w_gate_up.dtype
+
+            def to_dt(w, s):
+                if w.dtype == quant.FP8_DTYPE and s is not None:
+                    return quant.dequantize_fp8(w, s, dt)
+                if w.dtype == torch.uint8 and s is not None:
+                    return quant.dequantize_mxfp4(w, s, dt)
+                return w.to(dt)
+
+            self.w_gate_up.data[local_e, :I_loc].copy_(to_dt(*gate))
+            self.w_gate_up.data[local_e, I_loc:].copy_(to_dt(*up))
+            self.w_down.data[local_e].copy_(to_dt(*down))
+            return
+        dev = self.w_gate_up.device
+        stacks = (
+            (self.w_gate_up, self.w_gate_up_scale, slice(0, I_loc), gate),
+            (self.w_gate_up, self.w_gate_up_scale, slice(I_loc, None), up),
+            (self.w_down, self.w_down_scale, slice(None), down),
+        )
+        for codes, scales, rows, (w, s) in stacks:
+            q, qs = fmt.shard_to_codes(w, s, dev)
+            codes.data[local_e, rows].copy_(q)
+            scales.data[local_e, rows].copy_(qs)
+        # the sparse fallback (ops.linear_w8 / linear_w4 per expert) dequantizes
+        # into the shared scratch above the skinny kernels' batch limit
+        H = self.gate.shape[1]
+        ops.reserve_w8_scratch(dev, 2 * I_loc, H)
+        ops.reserve_w8_scratch(dev, H, I_loc)
 
     def load_expert(
         self, local_e: int, w1: torch.Tensor, w3: torch.Tensor,
-        w2: torch.Tensor,
+        w2: torch.Tensor, w1_scale: Optional[torch.Tensor] = None,
+        w3_scale: Optional[torch.Tensor] = None,
+        w2_scale: Optional[torch.Tensor] = None,
     ) -> None:
         """Load one expert from full-width HF tensors (w1=gate [I,H],
-        w3=up [I,H], w2=down [H,I]), applying this rank's shard."""
-        dt = self.w_gate_up.dtype
+        w3=up [I,H], w2=down [H,I]), applying this rank's shard. The
+        tensors may be pre-quantized codes with their ``weight_scale``: fp8
+        with f32 [out] scales (already expanded, quant.expand_scale), MXFP4
+        (uint8 [out, in/2]) with E8M0 scales [out, in/32]."""
         if self.expert_parallel:
-            self.w_gate_up.data[local_e].copy_(
-                torch.cat([w1, w3], dim=0).to(dt)
+            lo, hi = 0, self.inter_local
+        else:
+            r = comm.get_state().tp_rank
+            lo, hi = r * self.inter_local, (r + 1) * self.inter_local
+
+        def rows(w, s):  # gate / up: the scale rows follow the weight rows
+            return w[lo:hi], None if s is None else s[lo:hi]
+
+        if w2.dtype == torch.uint8:  # packed mxfp4: 2 per byte, 32 per scale
+            b = quant.MXFP4_BLOCK
+            if lo % b != 0 or hi % b != 0:
+                raise ValueError(
+                    f"mxfp4 needs the per-rank expert intermediate size "
+                    f"({self.inter_local}) to be a multiple of {b}"
+                )
+            if w2_scale is None:
+                raise ValueError("mxfp4 checkpoint weight without weight_scale")
+            w2_scale = quant.check_mxfp4_scale(
+                w2_scale, w2.shape[0], w2.shape[1] * 2
             )
-            self.w_down.data[local_e].copy_(w2.to(dt))
-            return
-        r = comm.get_state().tp_rank
-        lo, hi = r * self.inter_local, (r + 1) * self.inter_local
-        self.w_gate_up.data[local_e, : self.inter_local].copy_(w1[lo:hi].to(dt))
-        self.w_gate_up.data[local_e, self.inter_local :].copy_(w3[lo:hi].to(dt))
-        self.w_down.data[local_e].copy_(w2[:, lo:hi].to(dt))
+            down = w2[:, lo // 2:hi // 2], w2_scale[:, lo // b:hi // b]
+        else:  # a per-row (fp8) scale is not sliced with the columns
+            down = w2[:, lo:hi], w2_scale
+        self._store_expert(
+            local_e, rows(w1, w1_scale), rows(w3, w3_scale), down
+        )
+
+    @torch.no_grad()
+    def random_init_experts(self, which: str, std: float, generator) -> None:
+        """Quantized stacks have no normal_: draw the bf16 stack ``which``
+        ("w_gate_up" or "w_down") would have been and quantize it."""
+        fmt = self.weight_format
+        codes = getattr(self, which)
+        scales = getattr(self, which + "_scale")
+        tmp = torch.empty(
+            (*codes.shape[:2], codes.shape[2] * fmt.per_byte),
+            dtype=torch.bfloat16, device=codes.device,
+        ).normal_(0.0, std, generator=generator)
+        for le in range(codes.shape[0]):
+            q, qs = fmt.shard_to_codes(tmp[le], None, codes.device)
+            codes.data[le].copy_(q)
+            scales.data[le].copy_(qs)
+        ops.reserve_w8_scratch(codes.device, *tmp.shape[1:])
 
     def _forward_dense(self, x, topi, topw):
         """Capture-safe grouped path: every local expert runs on every
@@ -269,8 +380,23 @@ class MixtralMoE(nn.Module):
             "eth,te->th", ye.float(), w_loc
         ).to(x.dtype)
 
+    def _expert_linear(self, x, le: int, stack) -> torch.Tensor:
+        """x @ W^T for local expert ``le`` of a stack; quantized stacks go
+        through the format's ops.linear_w8 / linear_w4 on the expert's codes
+        (skinny kernel, dequant scratch + hipBLASLt, or the CPU reference)."""
+        fmt = self.weight_format
+        if fmt is None:
+            return torch.nn.functional.linear(x, stack[le])
+        scales = (
+            self.w_gate_up_scale if stack is self.w_gate_up
+            else self.w_down_scale
+        )
+        return getattr(ops, fmt.linear)(x, stack[le], scales[le])
+
     def _forward_sparse(self, x, topi, topw):
-        """Token-bucketed loop (prefill): exact FLOPs, host-side gather."""
+        """Token-bucketed loop (prefill): exact FLOPs, host-side gather.
+        With quantized experts it is also the only path beside the routed
+        kernel (CPU, non-bf16 activations, T > ROUTED_MAX_TOKENS)."""
         T = x.shape[0]
         out = torch.zeros_like(x)
         flat_i = topi.flatten()
@@ -285,9 +411,9 @@ class MixtralMoE(nn.Module):
                 continue
             rows = token_idx[sel]
             xe = x.index_select(0, rows)
-            gu = torch.nn.functional.linear(xe, self.w_gate_up[le])
+            gu = self._expert_linear(xe, le, self.w_gate_up)
             act = ops.silu_and_mul(gu)
-            ye = torch.nn.functional.linear(act, self.w_down[le])
+            ye = self._expert_linear(act, le, self.w_down)
             out.index_add_(
                 0, rows, ye * flat_w[sel].unsqueeze(1).to(ye.dtype)
             )
@@ -304,10 +430,14 @@ class MixtralMoE(nn.Module):
             self.moe_kernel == "routed"
             and x.is_cuda
             and x.dtype == torch.bfloat16
-            and self.w_gate_up.dtype == torch.bfloat16
+            and (
+                self.weight_format is not None
+                or self.w_gate_up.dtype == torch.bfloat16
+            )
             and x.shape[0] <= self.ROUTED_MAX_TOKENS
             and ops.moe_routed_supported(
-                x.shape[0], self.top_k, x.shape[1], self.inter_local
+                x.shape[0], self.top_k, x.shape[1], self.inter_local,
+                self.quantization,
             )
         )
 
@@ -321,9 +451,20 @@ class MixtralMoE(nn.Module):
             x.is_cuda and torch.cuda.is_current_stream_capturing()
         )
         if self._use_routed(x):
-            out = ops.moe_routed_mlp(
-                x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo
-            )
+            if self.weight_format is None:
+                out = ops.moe_routed_mlp(
+                    x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo
+                )
+            else:
+                out = ops.moe_routed_mlp(
+                    x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo,
+                    gate_up_scale=self.w_gate_up_scale,
+                    down_scale=self.w_down_scale,
+                    quantization=self.quantization,
+                )
+        elif self.weight_format is not None:
+            # no quantized dense-bmm path
+            out = self._forward_sparse(x, topi, topw)
         elif capturing or T <= self.DENSE_MAX_TOKENS:
             out = self._forward_dense(x, topi, topw)
         else:
@@ -378,15 +519,20 @@ class LlamaForCausalLM(nn.Module):
     ):
         super().__init__()
         self.config = config
-        if config.quantization is not None and config.num_local_experts > 0:
-            # the experts are stacked bmm weights and would need a grouped
-            # quantized kernel; quantizing only the attention projections
-            # (~5 % of the bytes) silently would be worse than refusing
+        if (
+            config.quantization is not None
+            and config.num_local_experts > 0
+            and getattr(config, "moe_kernel", "dense") != "routed"
+        ):
+            # the stacked experts are quantized for the routed grouped
+            # kernels only (MixtralMoE checks their shape limits); quantizing
+            # only the attention projections (~5 % of the bytes) silently
+            # would be worse than refusing
             raise ValueError(
-                f"quantization={config.quantization!r} does not support "
-                "mixture-of-experts models (num_local_experts > 0): the "
-                "stacked expert weights have no quantized (fp8 or mxfp4) "
-                "kernel"
+                f"quantization={config.quantization!r} supports "
+                "mixture-of-experts models (num_local_experts > 0) only "
+                "with moe_kernel='routed': the dense-bmm expert path has no "
+                "quantized (fp8 or mxfp4) form"
             )
         dtype = dtype or (
             torch.bfloat16 if config.dtype == "bfloat16" else torch.float32
@@ -456,13 +602,22 @@ class LlamaForCausalLM(nn.Module):
         # temporary in place of its weight and quantizes it
         quantized = {}
         for mod in self.modules():
-            if getattr(mod, "quantization", None) is not None:
-                quantized[id(mod.qweight)] = mod
+            if getattr(mod, "quantization", None) is None:
+                continue
+            if isinstance(mod, MixtralMoE):  # one draw per expert stack
+                for which in ("w_gate_up", "w_down"):
+                    quantized[id(getattr(mod, which))] = (
+                        lambda s, g, m=mod, w=which:
+                        m.random_init_experts(w, s, g)
+                    )
+                    quantized[id(getattr(mod, which + "_scale"))] = None
+            else:
+                quantized[id(mod.qweight)] = mod.random_init_weight
                 quantized[id(mod.weight_scale)] = None
         for p in self.parameters():
             if id(p) in quantized:
                 if quantized[id(p)] is not None:
-                    quantized[id(p)].random_init_weight(std, gen)
+                    quantized[id(p)](std, gen)
             elif p.dim() >= 2:
                 p.normal_(0.0, std, generator=gen)
             else:
@@ -596,12 +751,10 @@ class LlamaForCausalLM(nn.Module):
                     )
                     for le, j in enumerate(owned):
                         ep = p + f"block_sparse_moe.experts.{j}."
-                        moe.load_expert(
-                            le,
-                            get(ep + "w1.weight"),
-                            get(ep + "w3.weight"),
-                            get(ep + "w2.weight"),
+                        (w1, s1), (w3, s3), (w2, s2) = (
+                            get_w(ep + n) for n in ("w1", "w3", "w2")
                         )
+                        moe.load_expert(le, w1, w3, w2, s1, s3, s2)
                 else:
                     # fused layout (transformers >= 4.5x): mlp.gate.weight,
                     # mlp.experts.gate_up_proj [E, 2I, H], .down_proj [E, H, I]

@@ -674,15 +674,26 @@ MOE_ROUTED_MAX_PAIRS = 768
 MOE_ROUTED_MAX_TOPK = 8
 
 
-def moe_routed_supported(T: int, top_k: int, hidden: int, inter: int) -> bool:
-    """Shapes the routed MoE kernels take (dtype and device aside)."""
+# K step of the grouped GEMMs per expert weight format (``quantization``
+# name): hidden and intermediate size must be multiples of it
+MOE_ROUTED_K_STEP = {None: 64, "fp8": 128, "mxfp4": 128}
+_MOE_ROUTED_BINDING = {"fp8": "moe_routed_mlp_w8", "mxfp4": "moe_routed_mlp_w4"}
+
+
+def moe_routed_supported(
+    T: int, top_k: int, hidden: int, inter: int,
+    quantization: Optional[str] = None,
+) -> bool:
+    """Shapes the routed MoE kernels take (dtype and device aside) with
+    expert weights in the given format."""
+    step = MOE_ROUTED_K_STEP[quantization]
     return (
         1 <= T <= MOE_ROUTED_MAX_TOKENS
         and 1 <= top_k <= MOE_ROUTED_MAX_TOPK
         and T * top_k <= MOE_ROUTED_MAX_PAIRS
-        and hidden % 64 == 0
+        and hidden % step == 0
         and inter > 0
-        and inter % 64 == 0
+        and inter % step == 0
     )
 
 
@@ -693,6 +704,9 @@ def moe_routed_mlp(
     w_gate_up: torch.Tensor,
     w_down: torch.Tensor,
     expert_lo: int = 0,
+    gate_up_scale: Optional[torch.Tensor] = None,
+    down_scale: Optional[torch.Tensor] = None,
+    quantization: Optional[str] = None,
 ) -> torch.Tensor:
     """Routed mixture-of-experts SwiGLU MLP for decode-sized batches.
 
@@ -703,12 +717,31 @@ def moe_routed_mlp(
     nothing. The routing stays on the device and every grid depends on shapes
     only, so the call can be captured once and replayed with any routing.
     Bit-identical from run to run, and a row's result does not depend on the
-    other rows of the batch."""
+    other rows of the batch.
+
+    ``quantization`` ("fp8" or "mxfp4", a ``quant.WEIGHT_FORMATS`` name):
+    the weights are that format's codes, [E_local, 2I, H / per_byte] and
+    [E_local, H, I / per_byte], and ``gate_up_scale`` / ``down_scale`` their
+    scales: f32 [E_local, 2I] and [E_local, H] for fp8, E8M0 uint8
+    [E_local, 2I, H/32] and [E_local, H, I/32] for mxfp4. H and I must be
+    multiples of ``MOE_ROUTED_K_STEP[quantization]``."""
+    fmt = None
+    if quantization is not None:
+        from kserve_amd.ops import quant
+
+        quant.check_quantization(quantization)
+        fmt = quant.WEIGHT_FORMATS[quantization]
+        if gate_up_scale is None or down_scale is None:
+            raise ValueError(
+                f"quantization={quantization!r} needs gate_up_scale and "
+                "down_scale"
+            )
     if x.is_cuda:
         C = _native("moe_routed_mlp")
         T, H = x.shape
         P = T * topi.shape[1]
-        E, inter = w_gate_up.shape[0], w_down.shape[2]
+        E = w_gate_up.shape[0]
+        inter = w_down.shape[2] * (fmt.per_byte if fmt else 1)
         dev = x.device
         out = torch.empty_like(x)
         offsets = torch.empty(E + 1, dtype=torch.int32, device=dev)
@@ -717,13 +750,21 @@ def moe_routed_mlp(
         y = torch.empty(
             (C.moe_nsplit(inter), P, H), dtype=torch.float32, device=dev
         )
-        C.moe_routed_mlp(
-            out, x, topi, topw.float(), w_gate_up, w_down, int(expert_lo),
-            offsets, sorted_pair, act, y,
-        )
+        if fmt is None:
+            C.moe_routed_mlp(
+                out, x, topi, topw.float(), w_gate_up, w_down, int(expert_lo),
+                offsets, sorted_pair, act, y,
+            )
+        else:
+            getattr(C, _MOE_ROUTED_BINDING[quantization])(
+                out, x, topi, topw.float(), w_gate_up, gate_up_scale, w_down,
+                down_scale, int(expert_lo), offsets, sorted_pair, act, y,
+            )
         return out
     return torch_ref.moe_routed_mlp(
-        x, topi, topw, w_gate_up, w_down, expert_lo
+        x, topi, topw, w_gate_up, w_down, expert_lo,
+        gate_up_scale=gate_up_scale, down_scale=down_scale,
+        quantization=quantization,
     )
 
 

@@ -85,6 +85,14 @@ hipError_t ks_moe_routed_mlp(void*, const void*, const void*, const void*,
                              const void*, const void*, void*, void*, void*,
                              void*, int, int, int, int, int, int,
                              hipStream_t);
+hipError_t ks_moe_routed_mlp_w8(void*, const void*, const void*, const void*,
+                                const void*, const void*, const void*,
+                                const void*, void*, void*, void*, void*, int,
+                                int, int, int, int, int, hipStream_t);
+hipError_t ks_moe_routed_mlp_w4(void*, const void*, const void*, const void*,
+                                const void*, const void*, const void*,
+                                const void*, void*, void*, void*, void*, int,
+                                int, int, int, int, int, hipStream_t);
 hipError_t ks_kv_gather_pages(void*, const void*, const void*, int, int, long,
                               int, int, int, int, hipStream_t);
 hipError_t ks_kv_scatter_pages(const void*, const void*, const void*, int, int,
@@ -714,33 +722,39 @@ void lora_expand_add(at::Tensor& y, at::Tensor& tmp, at::Tensor& b_stack,
 
 int64_t moe_nsplit(int64_t inter) { return ks_moe_nsplit((int)inter); }
 
-void moe_routed_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
-                    at::Tensor& topw, at::Tensor& w_gate_up,
-                    at::Tensor& w_down, int64_t expert_lo,
-                    at::Tensor& offsets, at::Tensor& sorted_pair,
-                    at::Tensor& act, at::Tensor& y) {
-  // out [T, H] bf16 <- routed SwiGLU experts of x [T, H]; topi [T, k] int64
-  // global expert ids, topw [T, k] f32, w_gate_up [E, 2I, H], w_down
-  // [E, H, I]; pairs whose expert is outside [expert_lo, expert_lo + E)
-  // contribute nothing. The rest are workspaces (ops.moe_routed_mlp).
+// The routed MoE ops, after their own weight checks: out [T, H] bf16 <-
+// routed SwiGLU experts of x [T, H]; topi [T, k] int64 global expert ids,
+// topw [T, k] f32; the weights are [E, 2I, H / per_el] (gate rows, then up
+// rows) and [E, H, I / per_el] elements of the format's code type, per_el
+// logical weights per element; pairs whose expert is outside [expert_lo,
+// expert_lo + E) contribute nothing. BK is the format's K step. The rest are
+// workspaces (ops.moe_routed_mlp). Returns {T, k, H, I, E}.
+std::array<int64_t, 5> check_moe_routed(
+    int BK, int per_el, at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+    at::Tensor& topw, at::Tensor& w_gate_up, at::Tensor& w_down,
+    int64_t expert_lo, at::Tensor& offsets, at::Tensor& sorted_pair,
+    at::Tensor& act, at::Tensor& y) {
   CHECK_BF16_CONTIG(out);
   CHECK_BF16_CONTIG(x);
-  CHECK_BF16_CONTIG(w_gate_up);
-  CHECK_BF16_CONTIG(w_down);
   CHECK_BF16_CONTIG(act);
+  TORCH_CHECK(w_gate_up.is_cuda() && w_gate_up.is_contiguous() &&
+                  w_down.is_cuda() && w_down.is_contiguous() &&
+                  w_gate_up.scalar_type() == w_down.scalar_type(),
+              "expert weights must be contiguous GPU tensors of one dtype");
   TORCH_CHECK(x.dim() == 2 && w_gate_up.dim() == 3 && w_down.dim() == 3 &&
                   topi.dim() == 2,
               "moe_routed_mlp: x [T, H], topi [T, k], w_gate_up [E, 2I, H], "
               "w_down [E, H, I]");
   const int64_t T = x.size(0), H = x.size(1), k = topi.size(1);
-  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2) * per_el;
   TORCH_CHECK(T >= 1 && T <= 384 && T * k <= 768,
               "moe_routed_mlp needs 1 <= T <= 384 and T * k <= 768");
   TORCH_CHECK(k >= 1 && k <= 8, "moe_routed_mlp needs top-k <= 8");
   TORCH_CHECK(E >= 1 && E <= 256, "moe_routed_mlp needs <= 256 local experts");
-  TORCH_CHECK(H % 64 == 0 && I > 0 && I % 64 == 0,
-              "moe_routed_mlp needs H % 64 == 0 and I % 64 == 0");
-  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) == H &&
+  TORCH_CHECK(H % BK == 0 && I > 0 && I % BK == 0,
+              "moe_routed_mlp needs H % ", BK, " == 0 and I % ", BK,
+              " == 0 for this weight format");
+  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) * per_el == H &&
                   w_down.size(0) == E && w_down.size(1) == H,
               "moe_routed_mlp: expert weight shapes disagree");
   TORCH_CHECK(out.dim() == 2 && out.size(0) == T && out.size(1) == H,
@@ -764,13 +778,90 @@ void moe_routed_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
                   y.is_contiguous() &&
                   y.numel() == ks_moe_nsplit((int)I) * T * k * H,
               "y must be f32 [moe_nsplit(I), T * k, H]");
+  return {T, k, H, I, E};
+}
+
+void moe_routed_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+                    at::Tensor& topw, at::Tensor& w_gate_up,
+                    at::Tensor& w_down, int64_t expert_lo,
+                    at::Tensor& offsets, at::Tensor& sorted_pair,
+                    at::Tensor& act, at::Tensor& y) {
+  // bf16 experts: w_gate_up [E, 2I, H], w_down [E, H, I]
+  TORCH_CHECK(w_gate_up.scalar_type() == at::kBFloat16,
+              "w_gate_up must be bf16");
+  const auto s = check_moe_routed(64, 1, out, x, topi, topw, w_gate_up,
+                                  w_down, expert_lo, offsets, sorted_pair,
+                                  act, y);
   check_hip(ks_moe_routed_mlp(out.data_ptr(), x.data_ptr(), topi.data_ptr(),
                               topw.data_ptr(), w_gate_up.data_ptr(),
                               w_down.data_ptr(), offsets.data_ptr(),
                               sorted_pair.data_ptr(), act.data_ptr(),
-                              y.data_ptr(), (int)T, (int)k, (int)H, (int)I,
-                              (int)E, (int)expert_lo, current_stream()),
+                              y.data_ptr(), (int)s[0], (int)s[1], (int)s[2],
+                              (int)s[3], (int)s[4], (int)expert_lo,
+                              current_stream()),
             "moe_routed_mlp");
+}
+
+// a contiguous GPU scale tensor of the given dtype and shape
+void check_moe_scale(const char* name, const at::Tensor& t,
+                     at::ScalarType dtype, at::IntArrayRef shape) {
+  TORCH_CHECK(t.scalar_type() == dtype && t.is_cuda() && t.is_contiguous() &&
+                  t.sizes() == shape,
+              name, " must be a contiguous ", dtype, " GPU tensor of shape ",
+              shape);
+}
+
+void moe_routed_mlp_w8(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+                       at::Tensor& topw, at::Tensor& w_gate_up,
+                       at::Tensor& gate_up_scale, at::Tensor& w_down,
+                       at::Tensor& down_scale, int64_t expert_lo,
+                       at::Tensor& offsets, at::Tensor& sorted_pair,
+                       at::Tensor& act, at::Tensor& y) {
+  // fp8 experts: codes e4m3 [E, 2I, H] / [E, H, I], one f32 scale per
+  // output row [E, 2I] / [E, H]
+  TORCH_CHECK(w_gate_up.scalar_type() == at::kFloat8_e4m3fn,
+              "w_gate_up must be fp8_e4m3fn codes");
+  const auto s = check_moe_routed(128, 1, out, x, topi, topw, w_gate_up,
+                                  w_down, expert_lo, offsets, sorted_pair,
+                                  act, y);
+  check_moe_scale("gate_up_scale", gate_up_scale, at::kFloat,
+                  {s[4], 2 * s[3]});
+  check_moe_scale("down_scale", down_scale, at::kFloat, {s[4], s[2]});
+  check_hip(ks_moe_routed_mlp_w8(
+                out.data_ptr(), x.data_ptr(), topi.data_ptr(),
+                topw.data_ptr(), w_gate_up.data_ptr(), w_down.data_ptr(),
+                gate_up_scale.data_ptr(), down_scale.data_ptr(),
+                offsets.data_ptr(), sorted_pair.data_ptr(), act.data_ptr(),
+                y.data_ptr(), (int)s[0], (int)s[1], (int)s[2], (int)s[3],
+                (int)s[4], (int)expert_lo, current_stream()),
+            "moe_routed_mlp_w8");
+}
+
+void moe_routed_mlp_w4(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+                       at::Tensor& topw, at::Tensor& w_gate_up,
+                       at::Tensor& gate_up_scale, at::Tensor& w_down,
+                       at::Tensor& down_scale, int64_t expert_lo,
+                       at::Tensor& offsets, at::Tensor& sorted_pair,
+                       at::Tensor& act, at::Tensor& y) {
+  // MXFP4 experts: codes uint8 [E, 2I, H/2] / [E, H, I/2] (two E2M1 per
+  // byte), E8M0 scales uint8 [E, 2I, H/32] / [E, H, I/32]
+  TORCH_CHECK(w_gate_up.scalar_type() == at::kByte,
+              "w_gate_up must be uint8 (packed mxfp4 codes)");
+  const auto s = check_moe_routed(128, 2, out, x, topi, topw, w_gate_up,
+                                  w_down, expert_lo, offsets, sorted_pair,
+                                  act, y);
+  check_moe_scale("gate_up_scale", gate_up_scale, at::kByte,
+                  {s[4], 2 * s[3], s[2] / 32});
+  check_moe_scale("down_scale", down_scale, at::kByte,
+                  {s[4], s[2], s[3] / 32});
+  check_hip(ks_moe_routed_mlp_w4(
+                out.data_ptr(), x.data_ptr(), topi.data_ptr(),
+                topw.data_ptr(), w_gate_up.data_ptr(), w_down.data_ptr(),
+                gate_up_scale.data_ptr(), down_scale.data_ptr(),
+                offsets.data_ptr(), sorted_pair.data_ptr(), act.data_ptr(),
+                y.data_ptr(), (int)s[0], (int)s[1], (int)s[2], (int)s[3],
+                (int)s[4], (int)expert_lo, current_stream()),
+            "moe_routed_mlp_w4");
 }
 
 // Shared checks of the KV export/import ops. `caches` is K0, V0, K1, V1, ...
@@ -929,6 +1020,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K splits of the routed MoE down GEMM for an intermediate size");
   m.def("moe_routed_mlp", &moe_routed_mlp,
         "routed MoE SwiGLU MLP for decode batches (grouped MFMA GEMMs)");
+  m.def("moe_routed_mlp_w8", &moe_routed_mlp_w8,
+        "routed MoE SwiGLU MLP, fp8 e4m3 expert weights (per-row f32 scales)");
+  m.def("moe_routed_mlp_w4", &moe_routed_mlp_w4,
+        "routed MoE SwiGLU MLP, MXFP4 expert weights (E8M0 block scales)");
   m.def("kv_gather_pages", &kv_gather_pages,
         "gather a request's KV pages of every layer into one buffer");
   m.def("kv_scatter_pages", &kv_scatter_pages,

@@ -53,20 +53,38 @@
 // keeps 4 KB of W in flight per wave, the down kernel 2 KB and makes up for
 // it with the K split's extra workgroups.
 //
-// K order: BK = 64. Lane (kgrp = lane >> 4) holds W elements k0 + kgrp*16 +
-// [0, 16); MFMA kk in {0, 1} consumes elements kk*8..kk*8+7 of them, X chunk
-// kc = kgrp*2 + kk. That is wq_gemm.hip's fp8 arrangement, so the X tile
-// uses the same swizzle (derivation there).
+// K order, bf16: BK = 64. Lane (kgrp = lane >> 4) holds W elements k0 +
+// kgrp*16 + [0, 16); MFMA kk in {0, 1} consumes elements kk*8..kk*8+7 of
+// them, X chunk kc = kgrp*2 + kk. That is wq_gemm.hip's fp8 arrangement, so
+// the X tile uses the same swizzle (derivation in wq_formats.h).
+//
+// Quantized experts (weight-only fp8 and MXFP4, kserve_amd/ops/quant.py):
+// the GEMM kernel is a template over the weight format (MoeBf16, MoeFp8,
+// MoeMxfp4 below). Both quantized formats run BK = 128 with KK = 4: a lane
+// holds 32 consecutive K of its feature row, X chunk kc = kgrp*4 + kk, the
+// 16-chunk X tile row takes Mxfp4::chunk_perm. The step is not the bf16 step
+// with fewer bytes: fp8 keeps the bf16 kernel's 2 x 16 B per lane, stream and
+// step (4 KB in flight per wave in gate/up) and covers twice the K with
+// them; MXFP4 loads 16 B, exactly one MX block, plus that block's E8M0 scale
+// byte, and applies the scale inside the convert. Converts are exact. The
+// fp8 scale (one f32 per expert output row) multiplies the f32 accumulator
+// in the epilogue: gate and up each by their own row's scale before
+// SiLU*mul, down by scale * topw. At NT = 8 the double-buffered X tile is
+// 64 KB, the static LDS limit.
+//
+// The rule above holds per format: k_per_split rounds up to the format's BK,
+// so a row's summation order depends on the shapes and the format only.
 #include "common.h"
 #include "mfma_layouts.h"
 #include "skinny_shared.h"
+#include "wq_formats.h"
+
+extern "C" int ks_moe_nsplit(int I);
 
 namespace {
 
 constexpr int FEAT_PER_WAVE = 16;
 constexpr int NWAVES = 4;  // 64 features per workgroup
-constexpr int BK = 64;
-constexpr int ROW_CHUNKS = BK / 8;  // 16 B chunks in an X tile row
 
 constexpr int MAX_TOKENS = 384;
 constexpr int MAX_PAIRS = 768;
@@ -79,7 +97,68 @@ constexpr int MAX_EXPERTS = 256;  // local experts: 8 ballot bits, 1 thread each
 constexpr int SPLIT_MIN_K = 512;
 constexpr int MAX_SPLIT = 8;
 
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+// ---- weight formats of the grouped GEMMs ----
+//
+// BK, KK       K per step and MFMAs per step per token tile; a lane holds
+//              BK/4 consecutive K of its feature row
+// NLOAD        16 B register loads per lane, stream and step
+// STEP_SCALE   one E8M0 scale byte per lane, stream and step (a VM
+//              operation of its own), applied in the convert
+// OUT_SCALE    one f32 scale per expert output row, applied in the epilogue
+// row_bytes    bytes that k elements of a W row occupy
+// chunk_perm   the format's part of the X tile swizzle (wq_formats.h)
+// frag         the 8 bf16 of MFMA kk from a lane's registers of one step
+struct MoeBf16 {
+  static constexpr int BK = 64;
+  static constexpr int KK = 2;
+  static constexpr int NLOAD = 2;
+  static constexpr bool STEP_SCALE = false;
+  static constexpr bool OUT_SCALE = false;
+  using scale_t = float;  // unused
+  static __device__ __forceinline__ long row_bytes(long k) { return k * 2; }
+  static __device__ __forceinline__ int chunk_perm(int kc) {
+    return Fp8::chunk_perm(kc);
+  }
+  static __device__ __forceinline__ bf16x8_t frag(const u32x4_t (&w)[NLOAD],
+                                                  int kk, float) {
+    return __builtin_bit_cast(bf16x8_t, w[kk]);
+  }
+};
+
+struct MoeFp8 {
+  static constexpr int BK = 128;
+  static constexpr int KK = 4;
+  static constexpr int NLOAD = 2;
+  static constexpr bool STEP_SCALE = false;
+  static constexpr bool OUT_SCALE = true;
+  using scale_t = float;
+  static __device__ __forceinline__ long row_bytes(long k) { return k; }
+  static __device__ __forceinline__ int chunk_perm(int kc) {
+    return Mxfp4::chunk_perm(kc);
+  }
+  // 32 fp8 bytes in two loads: MFMA kk takes dwords 2*(kk&1), +1 of load kk/2
+  static __device__ __forceinline__ bf16x8_t frag(const u32x4_t (&w)[NLOAD],
+                                                  int kk, float) {
+    return Fp8::cvt8(w[kk >> 1], kk & 1, 1.0f);
+  }
+};
+
+struct MoeMxfp4 {
+  static constexpr int BK = 128;
+  static constexpr int KK = 4;
+  static constexpr int NLOAD = 1;
+  static constexpr bool STEP_SCALE = true;
+  static constexpr bool OUT_SCALE = false;
+  using scale_t = unsigned char;
+  static __device__ __forceinline__ long row_bytes(long k) { return k / 2; }
+  static __device__ __forceinline__ int chunk_perm(int kc) {
+    return Mxfp4::chunk_perm(kc);
+  }
+  static __device__ __forceinline__ bf16x8_t frag(const u32x4_t (&w)[NLOAD],
+                                                  int kk, float sc) {
+    return Mxfp4::cvt8(w[0], kk, sc);
+  }
+};
 
 // local expert of a routed id, or -1 (remote under EP, or not an expert)
 __device__ __forceinline__ int local_expert(long long id, int expert_lo,
@@ -164,29 +243,33 @@ __global__ __launch_bounds__(256) void moe_align_kernel(
 // ---- 2, 3. grouped GEMMs ----
 //
 // NS W streams per wave: 2 (gate rows and up rows) or 1 (down rows).
-template <int NS>
-struct WRegs {
-  u32x4_t w[NS][2];
+// What one K-step of W occupies in a lane's registers; s is only written
+// and read with STEP_SCALE.
+template <class Fmt, int NS>
+struct MoeRegs {
+  u32x4_t w[NS][Fmt::NLOAD];
+  unsigned int s[NS];
 };
 
-// swizzle of the X tile: wq_gemm.hip Fp8::chunk_perm (an involution)
-__device__ __forceinline__ int chunk_perm(int kc) {
-  return kc ^ ((kc >> 1) & 1);
-}
-
 // grid: x = feature block of 64, y = local expert, z = chunk * nsplit + split
-template <int NT, bool GATE_UP>
+template <class Fmt, int NT, bool GATE_UP>
 __global__ __launch_bounds__(256) void moe_gemm_kernel(
     short* __restrict__ act_out,  // GATE_UP: [P][N] bf16 by sorted position
     float* __restrict__ y_out,    // !GATE_UP: [nsplit][P][N] f32 by pair id
     const short* __restrict__ xin,  // GATE_UP: x [T][K]; else act [P][K]
-    const short* __restrict__ w,    // GATE_UP: [E][2N][K]; else [E][N][K]
+    // GATE_UP: [E][2N] rows, else [E][N] rows, of row_bytes(K) each
+    const unsigned char* __restrict__ w,
+    // OUT_SCALE: f32 [E][2N] / [E][N]; STEP_SCALE: E8M0 [E][2N][K/32] /
+    // [E][N][K/32]; bf16: unused
+    const typename Fmt::scale_t* __restrict__ scale,
     const int* __restrict__ offsets, const int* __restrict__ sorted_pair,
     const float* __restrict__ topw,  // [P]
     const int N, const int K, const int P, const int top_k, const int nsplit,
     const int k_per_split) {
   constexpr int NS = GATE_UP ? 2 : 1;
-  using Regs = WRegs<NS>;
+  constexpr int BK = Fmt::BK;
+  constexpr int ROW_CHUNKS = BK / 8;  // 16 B chunks in an X tile row
+  using Regs = MoeRegs<Fmt, NS>;
 
   const int e = blockIdx.y;
   const int chunk = blockIdx.z / nsplit;
@@ -218,12 +301,20 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
 
   const int m_local = lane & 15;
   const int kgrp = lane >> 4;
-  // this lane's W streams: its feature row(s), 2 x 16 bytes per K-step
+  // this lane's W streams: its feature row(s), NLOAD x 16 bytes per K-step
+  // from K offset kgrp * BK/4, and with STEP_SCALE the scale byte of that
+  // block (BK/4 = 32 = one MX block)
   const int frow = f_base + wave * FEAT_PER_WAVE + m_local;
-  const short* wrow[NS];
+  const unsigned char* wrow[NS];
+  const unsigned char* srow[NS];
 #pragma unroll
-  for (int s = 0; s < NS; ++s)
-    wrow[s] = w + (((long)e * NS + s) * N + frow) * K + kgrp * 16;
+  for (int s = 0; s < NS; ++s) {
+    const long row = ((long)e * NS + s) * N + frow;
+    wrow[s] = w + row * Fmt::row_bytes(K) + Fmt::row_bytes(kgrp * (BK / 4));
+    srow[s] = nullptr;
+    if constexpr (Fmt::STEP_SCALE)
+      srow[s] = scale + row * (K / 32) + kgrp;
+  }
 
   // this lane's X sources, fixed over K: tile row -> sorted position ->
   // (GATE_UP) token of the pair there. Rows past the count clamp to the last.
@@ -235,7 +326,7 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
     const int g = i * 64 + lane;
     if (!PAD || i < NINSTR) {
       const int row = g / ROW_CHUNKS;
-      const int kc_src = chunk_perm((g & (ROW_CHUNKS - 1)) ^
+      const int kc_src = Fmt::chunk_perm((g & (ROW_CHUNKS - 1)) ^
                                     (row & (ROW_CHUNKS - 1)));
       const int pos = row_lo + min(row, rows - 1);
       const int src_row = GATE_UP ? sorted_pair[pos] / top_k : pos;
@@ -250,7 +341,7 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
 
   auto lds_row_idx = [](int row, int kc) {
     return (row * ROW_CHUNKS +
-            (chunk_perm(kc) ^ (row & (ROW_CHUNKS - 1)))) * 8;  // shorts
+            (Fmt::chunk_perm(kc) ^ (row & (ROW_CHUNKS - 1)))) * 8;  // shorts
   };
   auto stage = [&](int buf, int k0) {
 #pragma unroll
@@ -266,22 +357,35 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
   auto load_w = [&](Regs& r, int k0) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-      r.w[s][0] = *reinterpret_cast<const u32x4_t*>(wrow[s] + k0);
-      r.w[s][1] = *reinterpret_cast<const u32x4_t*>(wrow[s] + k0 + 8);
+      const unsigned char* p = wrow[s] + Fmt::row_bytes(k0);
+#pragma unroll
+      for (int l = 0; l < Fmt::NLOAD; ++l)
+        r.w[s][l] = *reinterpret_cast<const u32x4_t*>(p + l * 16);
+      if constexpr (Fmt::STEP_SCALE) r.s[s] = srow[s][k0 / 32];
     }
   };
 
-  // Per step a wave issues NW VM operations, in this order: 2*NS W register
-  // loads, NI X LDS loads. Waiting for NW outstanding means the whole
-  // previous step has landed. A load added to the K loop is added here.
-  constexpr int NW = 2 * NS + NI;
+  // Per step a wave issues NW VM operations, in this order: per stream NLOAD
+  // W register loads and, with STEP_SCALE, one scale byte load; then NI X
+  // LDS loads. Waiting for NW outstanding means the whole previous step has
+  // landed. A load added to the K loop is added here.
+  constexpr int NW = NS * (Fmt::NLOAD + (Fmt::STEP_SCALE ? 1 : 0)) + NI;
   constexpr int WAIT_NEXT = waitcnt_vmcnt(NW);
   constexpr int WAIT_0 = waitcnt_vmcnt(0);
 
   auto compute = [&](const int buf, const Regs& use) {
+    float sc[NS];
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int kc = kgrp * 2 + kk;
+    for (int s = 0; s < NS; ++s) {
+      sc[s] = 1.0f;
+      if constexpr (Fmt::STEP_SCALE) sc[s] = e8m0_to_float(use.s[s]);
+    }
+#pragma unroll
+    for (int kk = 0; kk < Fmt::KK; ++kk) {
+      const int kc = kgrp * Fmt::KK + kk;
+      bf16x8_t b[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) b[s] = Fmt::frag(use.w[s], kk, sc[s]);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         if (t * 16 < rows) {  // wave-uniform: tiles past the count do no work
@@ -289,8 +393,7 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
               &tile[buf][lds_row_idx(t * 16 + m_local, kc)]);
 #pragma unroll
           for (int s = 0; s < NS; ++s)
-            acc[s][t] = mfma16x16x32(
-                a, __builtin_bit_cast(bf16x8_t, use.w[s][kk]), acc[s][t]);
+            acc[s][t] = mfma16x16x32(a, b[s], acc[s][t]);
         }
       }
     }
@@ -331,7 +434,14 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
   }
 
   // ---- epilogue: C row = tile row, col = feature ----
+  // OUT_SCALE: each stream's accumulator takes its own row's scale in f32
   const int feat = f_base + wave * FEAT_PER_WAVE + MFMA_C_COL(lane);
+  float osc[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    osc[s] = 1.0f;
+    if constexpr (Fmt::OUT_SCALE) osc[s] = scale[((long)e * NS + s) * N + feat];
+  }
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     if (t * 16 >= rows) continue;
@@ -341,13 +451,18 @@ __global__ __launch_bounds__(256) void moe_gemm_kernel(
       if (r < rows) {
         const int pos = row_lo + r;
         if constexpr (GATE_UP) {
-          const float g = acc[0][t][reg];
-          const float a = g / (1.0f + __expf(-g)) * acc[NS - 1][t][reg];
+          float g = acc[0][t][reg], u = acc[NS - 1][t][reg];
+          if constexpr (Fmt::OUT_SCALE) {
+            g *= osc[0];
+            u *= osc[NS - 1];
+          }
+          const float a = g / (1.0f + __expf(-g)) * u;
           act_out[(long)pos * N + feat] = float_to_bf16_bits(a);
         } else {
           const int pair = sorted_pair[pos];
-          y_out[((long)split * P + pair) * N + feat] =
-              acc[0][t][reg] * topw[pair];
+          float tw = topw[pair];
+          if constexpr (Fmt::OUT_SCALE) tw *= osc[0];
+          y_out[((long)split * P + pair) * N + feat] = acc[0][t][reg] * tw;
         }
       }
     }
@@ -377,45 +492,54 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
   *reinterpret_cast<short4_t*>(out + (long)t * H + h) = o;
 }
 
-template <int NT>
-void launch_gemms(short* act, float* y, const short* x, const short* w_gate_up,
-                  const short* w_down, const int* offsets,
+template <class Fmt, int NT>
+void launch_gemms(short* act, float* y, const short* x,
+                  const unsigned char* w_gate_up, const unsigned char* w_down,
+                  const typename Fmt::scale_t* gate_up_scale,
+                  const typename Fmt::scale_t* down_scale, const int* offsets,
                   const int* sorted_pair, const float* topw, int T, int top_k,
                   int H, int I, int E, int nsplit, int k_per_split,
                   hipStream_t stream) {
   const int P = T * top_k;
   const int nchunks = cdiv(T, NT * 16);
-  hipLaunchKernelGGL((moe_gemm_kernel<NT, true>), dim3(I / 64, E, nchunks),
-                     dim3(256), 0, stream, act, (float*)nullptr, x, w_gate_up,
-                     offsets, sorted_pair, topw, I, H, P, top_k, 1, H);
-  hipLaunchKernelGGL((moe_gemm_kernel<NT, false>),
+  hipLaunchKernelGGL((moe_gemm_kernel<Fmt, NT, true>),
+                     dim3(I / 64, E, nchunks), dim3(256), 0, stream, act,
+                     (float*)nullptr, x, w_gate_up, gate_up_scale, offsets,
+                     sorted_pair, topw, I, H, P, top_k, 1, H);
+  hipLaunchKernelGGL((moe_gemm_kernel<Fmt, NT, false>),
                      dim3(H / 64, E, nchunks * nsplit), dim3(256), 0, stream,
-                     (short*)nullptr, y, act, w_down, offsets, sorted_pair,
-                     topw, H, I, P, top_k, nsplit, k_per_split);
-}
-
-}  // namespace
-
-extern "C" int ks_moe_nsplit(int I) {
-  return max(1, min(MAX_SPLIT, I / SPLIT_MIN_K));
+                     (short*)nullptr, y, act, w_down, down_scale, offsets,
+                     sorted_pair, topw, H, I, P, top_k, nsplit, k_per_split);
 }
 
 // Workspaces (device): offsets int32 [E + 1], sorted_pair int32 [T*k], act
 // bf16 [T*k][I], y f32 [ks_moe_nsplit(I)][T*k][H]. Nothing needs clearing.
-extern "C" hipError_t ks_moe_routed_mlp(
-    void* out, const void* x, const void* topi, const void* topw,
-    const void* w_gate_up, const void* w_down, void* offsets,
-    void* sorted_pair, void* act, void* y, int T, int top_k, int H, int I,
-    int E, int expert_lo, hipStream_t stream) {
+template <class Fmt>
+hipError_t moe_routed_mlp(void* out, const void* x, const void* topi,
+                          const void* topw, const void* w_gate_up,
+                          const void* w_down, const void* gate_up_scale,
+                          const void* down_scale, void* offsets,
+                          void* sorted_pair, void* act, void* y, int T,
+                          int top_k, int H, int I, int E, int expert_lo,
+                          hipStream_t stream) {
+  constexpr int BK = Fmt::BK;
+  // H and I are both a K and an N dimension: N needs % 64, K needs % BK
+  static_assert(BK % (NWAVES * FEAT_PER_WAVE) == 0, "BK covers the N multiple");
   if (T < 1 || T > MAX_TOKENS || top_k < 1 || top_k > MAX_TOPK ||
       T * top_k > MAX_PAIRS || E < 1 || E > MAX_EXPERTS || H <= 0 ||
-      H % 64 != 0 || I <= 0 || I % 64 != 0)
+      H % BK != 0 || I <= 0 || I % BK != 0)
     return hipErrorInvalidValue;
-  // 16-byte global_load_lds sources and W register loads; rows are
-  // multiples of 128 bytes, so every row start keeps the base alignment
+  if ((Fmt::STEP_SCALE || Fmt::OUT_SCALE) &&
+      (gate_up_scale == nullptr || down_scale == nullptr))
+    return hipErrorInvalidValue;
+  // 16-byte global_load_lds sources and W register loads; W rows are
+  // multiples of 64 bytes in every format (K % BK == 0), so every row start
+  // keeps the base alignment
   if (((uintptr_t)x & 15) != 0 || ((uintptr_t)act & 15) != 0 ||
       ((uintptr_t)w_gate_up & 15) != 0 || ((uintptr_t)w_down & 15) != 0 ||
-      ((uintptr_t)y & 15) != 0 || ((uintptr_t)out & 7) != 0)
+      ((uintptr_t)y & 15) != 0 || ((uintptr_t)out & 7) != 0 ||
+      (Fmt::OUT_SCALE && ((((uintptr_t)gate_up_scale) & 3) != 0 ||
+                          (((uintptr_t)down_scale) & 3) != 0)))
     return hipErrorInvalidValue;
   const int P = T * top_k;
   const int nsplit = ks_moe_nsplit(I);
@@ -425,11 +549,13 @@ extern "C" hipError_t ks_moe_routed_mlp(
                      (int*)offsets, (int*)sorted_pair, (const long long*)topi,
                      P, expert_lo, E);
 #define CASE(nt)                                                           \
-  launch_gemms<nt>((short*)act, (float*)y, (const short*)x,                \
-                   (const short*)w_gate_up, (const short*)w_down,          \
-                   (const int*)offsets, (const int*)sorted_pair,           \
-                   (const float*)topw, T, top_k, H, I, E, nsplit,          \
-                   k_per_split, stream)
+  launch_gemms<Fmt, nt>(                                                   \
+      (short*)act, (float*)y, (const short*)x,                             \
+      (const unsigned char*)w_gate_up, (const unsigned char*)w_down,       \
+      (const typename Fmt::scale_t*)gate_up_scale,                         \
+      (const typename Fmt::scale_t*)down_scale, (const int*)offsets,       \
+      (const int*)sorted_pair, (const float*)topw, T, top_k, H, I, E,      \
+      nsplit, k_per_split, stream)
   // rows per chunk = 16 * NT: the smallest tile count that holds T, up to 8
   if (T <= 16) CASE(1);
   else if (T <= 32) CASE(2);
@@ -442,4 +568,47 @@ extern "C" hipError_t ks_moe_routed_mlp(
                      E);
   HIP_CHECK_KERNEL();
   return hipSuccess;
+}
+
+}  // namespace
+
+extern "C" int ks_moe_nsplit(int I) {
+  return max(1, min(MAX_SPLIT, I / SPLIT_MIN_K));
+}
+
+extern "C" hipError_t ks_moe_routed_mlp(
+    void* out, const void* x, const void* topi, const void* topw,
+    const void* w_gate_up, const void* w_down, void* offsets,
+    void* sorted_pair, void* act, void* y, int T, int top_k, int H, int I,
+    int E, int expert_lo, hipStream_t stream) {
+  return moe_routed_mlp<MoeBf16>(out, x, topi, topw, w_gate_up, w_down,
+                                 nullptr, nullptr, offsets, sorted_pair, act,
+                                 y, T, top_k, H, I, E, expert_lo, stream);
+}
+
+// fp8 experts: codes [E][2I][H] / [E][H][I] e4m3, scales f32 [E][2I] / [E][H]
+extern "C" hipError_t ks_moe_routed_mlp_w8(
+    void* out, const void* x, const void* topi, const void* topw,
+    const void* w_gate_up, const void* w_down, const void* gate_up_scale,
+    const void* down_scale, void* offsets, void* sorted_pair, void* act,
+    void* y, int T, int top_k, int H, int I, int E, int expert_lo,
+    hipStream_t stream) {
+  return moe_routed_mlp<MoeFp8>(out, x, topi, topw, w_gate_up, w_down,
+                                gate_up_scale, down_scale, offsets,
+                                sorted_pair, act, y, T, top_k, H, I, E,
+                                expert_lo, stream);
+}
+
+// MXFP4 experts: codes [E][2I][H/2] / [E][H][I/2], E8M0 scales
+// [E][2I][H/32] / [E][H][I/32]
+extern "C" hipError_t ks_moe_routed_mlp_w4(
+    void* out, const void* x, const void* topi, const void* topw,
+    const void* w_gate_up, const void* w_down, const void* gate_up_scale,
+    const void* down_scale, void* offsets, void* sorted_pair, void* act,
+    void* y, int T, int top_k, int H, int I, int E, int expert_lo,
+    hipStream_t stream) {
+  return moe_routed_mlp<MoeMxfp4>(out, x, topi, topw, w_gate_up, w_down,
+                                  gate_up_scale, down_scale, offsets,
+                                  sorted_pair, act, y, T, top_k, H, I, E,
+                                  expert_lo, stream);
 }

@@ -219,6 +219,9 @@ class WeightFormat:
     # slicing, so scales are per rank; a pre-quantized one is checked and
     # moved; the other format's codes are refused.
     shard_to_codes: Callable
+    # (codes [out, in / per_byte], scale, dtype) -> the [out, in] weight they
+    # stand for (the CPU reference of the routed MoE op)
+    dequantize: Callable
 
     def storage_shapes(self, out_features: int, in_features: int):
         """Shapes of (qweight, weight_scale) for a logical [out, in]."""
@@ -243,9 +246,11 @@ WEIGHT_FORMATS = {
     "fp8": WeightFormat(
         "fp8", FP8_DTYPE, torch.float32, per_byte=1, block=None,
         linear="linear_w8", shard_to_codes=_fp8_shard,
+        dequantize=dequantize_fp8,
     ),
     "mxfp4": WeightFormat(
         "mxfp4", torch.uint8, torch.uint8, per_byte=2, block=MXFP4_BLOCK,
         linear="linear_w4", shard_to_codes=_mxfp4_shard,
+        dequantize=dequantize_mxfp4,
     ),
 }

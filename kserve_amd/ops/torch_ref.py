@@ -407,22 +407,38 @@ def moe_routed_mlp(
     w_gate_up: torch.Tensor,  # [E_local, 2I, H] (gate rows, then up rows)
     w_down: torch.Tensor,     # [E_local, H, I]
     expert_lo: int = 0,
+    gate_up_scale: Optional[torch.Tensor] = None,
+    down_scale: Optional[torch.Tensor] = None,
+    quantization: Optional[str] = None,
 ) -> torch.Tensor:
     """Routed MoE SwiGLU MLP, fp32 reference: out[t] = sum_j topw[t, j] *
     down_e(silu(gate_e(x[t])) * up_e(x[t])) with e = topi[t, j] - expert_lo.
     Pairs whose e is outside [0, E_local) contribute nothing (remote experts
     under EP, or ids that name no expert). The activation is rounded to x's
-    dtype before the down projection, the output once at the end."""
-    E, inter = w_gate_up.shape[0], w_down.shape[2]
+    dtype before the down projection, the output once at the end. With
+    ``quantization`` the weights are that format's codes and each routed
+    expert is dequantized (exactly, to f32) with its scales first."""
+    E = w_gate_up.shape[0]
+    fmt = None
+    if quantization is not None:
+        from kserve_amd.ops import quant
+
+        fmt = quant.WEIGHT_FORMATS[quantization]
+    inter = w_down.shape[2] * (fmt.per_byte if fmt else 1)
     xf = x.float()
     out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
     for le in range(E):
         t_idx, j_idx = (topi == expert_lo + le).nonzero(as_tuple=True)
         if t_idx.numel() == 0:
             continue
-        gu = xf[t_idx] @ w_gate_up[le].float().t()
+        if fmt is None:
+            w_gu, w_d = w_gate_up[le].float(), w_down[le].float()
+        else:
+            w_gu = fmt.dequantize(w_gate_up[le], gate_up_scale[le])
+            w_d = fmt.dequantize(w_down[le], down_scale[le])
+        gu = xf[t_idx] @ w_gu.t()
         act = torch.nn.functional.silu(gu[:, :inter]) * gu[:, inter:]
-        ye = act.to(x.dtype).float() @ w_down[le].float().t()
+        ye = act.to(x.dtype).float() @ w_d.t()
         out.index_add_(0, t_idx, ye * topw[t_idx, j_idx].float().unsqueeze(1))
     return out.to(x.dtype)
 

@@ -38,6 +38,9 @@ parser.add_argument("--w4", action="store_true",
 parser.add_argument("--moe", action="store_true",
                     help="routed MoE MLP against the dense-bmm path, one "
                          "Mixtral-8x7B layer (profiles/moe_routed.md)")
+parser.add_argument("--quantization", choices=("fp8", "mxfp4"), default=None,
+                    help="--moe: the routed layer with experts in this "
+                         "format against the routed bf16 layer")
 parser.add_argument("--out", default=None,
                     help="--w8/--w4/--moe: also write the table as markdown "
                          "here")
@@ -399,8 +402,113 @@ def bench_moe():
             f.write("\n".join(lines) + "\n")
 
 
+def bench_moe_quant(q):
+    """--moe --quantization q: the routed layer with fp8 / MXFP4 experts
+    against the routed bf16 layer at the same T and routing, same process,
+    rounds interleaved as in bench_moe. The quantized weights are the bf16
+    layer's, quantized per expert. Bytes are what the routed experts occupy in
+    the format (codes and scales); the bound is bytes at 8 TB/s or the routed
+    FLOPs at 2.5 PFLOP/s, whichever is larger. Times are whole calls of
+    ops.moe_routed_mlp (align, two GEMMs, combine and the workspace
+    allocations), so TB/s and % of bound are layer figures, not kernel ones."""
+    import statistics
+
+    from kserve_amd import ops
+    from kserve_amd.engine.config import ModelConfig
+    from kserve_amd.models.llama import MixtralMoE
+
+    H, I, E, k = 4096, 14336, 8, 2
+    PEAK_BW, PEAK_FLOPS = 8.0e12, 2.5e15
+    rounds = 5
+    gen = torch.Generator(device=dev).manual_seed(0)
+    qcfg = ModelConfig.mixtral_8x7b()
+    qcfg.quantization, qcfg.moe_kernel = q, "routed"
+    with torch.device(dev):
+        ref = MixtralMoE(ModelConfig.mixtral_8x7b(), dtype=torch.bfloat16)
+        moe = MixtralMoE(qcfg, dtype=torch.bfloat16)
+    ref.w_gate_up.data.normal_(0, H ** -0.5, generator=gen)
+    ref.w_down.data.normal_(0, I ** -0.5, generator=gen)
+    fmt = moe.weight_format
+    for e in range(E):
+        for name in ("w_gate_up", "w_down"):
+            codes, scale = fmt.shard_to_codes(getattr(ref, name)[e], None, dev)
+            getattr(moe, name).data[e].copy_(codes)
+            getattr(moe, name + "_scale").data[e].copy_(scale)
+    per_expert = sum(
+        t[0].numel() * t.element_size()
+        for t in (moe.w_gate_up, moe.w_down, moe.w_gate_up_scale,
+                  moe.w_down_scale)
+    )
+
+    def timed(fn, iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(iters):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / iters * 1000
+
+    lines = [
+        f"| T | experts routed | bf16 us | spread | {q} us | spread "
+        f"| bf16/{q} | {q} MB read | {q} TB/s | bound | % of bound |",
+        "|---|---|---|---|---|---|---|---|---|---|---|",
+    ]
+    print(lines[0]); print(lines[1])
+    for T in (1, 4, 16, 64, 128, 384):
+        x = torch.randn(T, H, dtype=torch.bfloat16, device=dev, generator=gen)
+        logits = torch.randn(T, E, device=dev, generator=gen)
+        topw, topi = torch.softmax(logits, -1).topk(k, -1)
+        topw = topw / topw.sum(-1, keepdim=True)
+
+        def fb():
+            return ops.moe_routed_mlp(
+                x, topi, topw, ref.w_gate_up, ref.w_down, 0
+            )
+
+        def fq():
+            return ops.moe_routed_mlp(
+                x, topi, topw, moe.w_gate_up, moe.w_down, 0,
+                gate_up_scale=moe.w_gate_up_scale,
+                down_scale=moe.w_down_scale, quantization=q,
+            )
+
+        iters = max(args.iters, 10) * 4  # 200 calls: >= 15 ms per window
+        res = {"b": [], "q": []}
+        for r in range(rounds + 1):  # round 0 is warm-up
+            for key, fn in (("b", fb), ("q", fq)):
+                t = timed(fn, iters)
+                if r:
+                    res[key].append(t)
+        b, qt = (statistics.median(res[key]) for key in "bq")
+        sb, sq = (
+            (max(res[key]) - min(res[key])) / statistics.median(res[key])
+            for key in "bq"
+        )
+        routed = int(topi.unique().numel())
+        wbytes = routed * per_expert
+        flops = 2 * T * k * 3 * H * I
+        t_bw, t_fl = wbytes / PEAK_BW * 1e6, flops / PEAK_FLOPS * 1e6
+        line = (
+            f"| {T} | {routed} | {b:.1f} | {sb:.1%} | {qt:.1f} | {sq:.1%} "
+            f"| {b / qt:.2f} | {wbytes / 1e6:.0f} | {wbytes / qt / 1e6:.2f} "
+            f"| {'bytes' if t_bw >= t_fl else 'FLOPs'} "
+            f"| {max(t_bw, t_fl) / qt:.0%} |"
+        )
+        print(line, flush=True)
+        lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 if args.moe:
-    bench_moe()
+    if args.quantization:
+        bench_moe_quant(args.quantization)
+    else:
+        bench_moe()
     sys.exit(0)
 if args.w8:
     bench_w8()
