@@ -441,6 +441,29 @@ class MixtralMoE(nn.Module):
             )
         )
 
+    # Batches the routed prefill kernels (ops.moe_routed_prefill_mlp) take
+    # over from the sparse loop: ROUTED_MAX_TOKENS < T <=
+    # ROUTED_PREFILL_MAX_TOKENS, bf16 experts. On a Mixtral-8x7B layer they
+    # are 2.15x / 1.65x / 1.30x the sparse loop at 512 / 1024 / 2048 tokens
+    # and 0.94x / 0.76x at 4096 / 8192, where the per-expert library GEMMs
+    # are large enough to win (profiles/moe_routed.md, "Prefill").
+    ROUTED_PREFILL_MAX_TOKENS = 2048
+
+    def _use_routed_prefill(self, x: torch.Tensor) -> bool:
+        return (
+            self.moe_kernel == "routed"
+            and x.is_cuda
+            and x.dtype == torch.bfloat16
+            and self.weight_format is None
+            and self.w_gate_up.dtype == torch.bfloat16
+            and self.ROUTED_MAX_TOKENS < x.shape[0]
+            <= self.ROUTED_PREFILL_MAX_TOKENS
+            and self.experts_per_rank <= 256
+            and ops.moe_routed_prefill_supported(
+                x.shape[0], self.top_k, x.shape[1], self.inter_local
+            )
+        )
+
     def forward(self, x: torch.Tensor, meta=None) -> torch.Tensor:
         T = x.shape[0]
         router_logits = torch.nn.functional.linear(x.float(), self.gate.float())
@@ -462,6 +485,10 @@ class MixtralMoE(nn.Module):
                     down_scale=self.w_down_scale,
                     quantization=self.quantization,
                 )
+        elif self._use_routed_prefill(x):
+            out = ops.moe_routed_prefill_mlp(
+                x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo
+            )
         elif self.weight_format is not None:
             # no quantized dense-bmm path
             out = self._forward_sparse(x, topi, topw)

@@ -768,6 +768,76 @@ def moe_routed_mlp(
     )
 
 
+# tokens per call of the routed MoE prefill kernels: the wrapper walks a
+# larger batch in chunks of this many rows (rows are independent, so the
+# result is the same), which bounds act and y at chunk * k * (2 I + 4 H)
+# bytes: 117 MB and 67 MB for a Mixtral-8x7B layer instead of 470 MB and
+# 268 MB at 8192 tokens
+MOE_PREFILL_CHUNK_TOKENS = 2048
+# grid order of the grouped GEMMs: False = feature block fastest, True = row
+# tile fastest (csrc/moe_prefill.hip; measured in profiles/moe_routed.md)
+MOE_PREFILL_ROW_FAST = False
+
+
+def moe_routed_prefill_supported(
+    T: int, top_k: int, hidden: int, inter: int
+) -> bool:
+    """Shapes ops.moe_routed_prefill_mlp takes (dtype and device aside): any
+    T >= 1 (batches above MOE_PREFILL_CHUNK_TOKENS run in chunks), top-k <= 8,
+    hidden % 128 == 0 and inter % 64 == 0."""
+    return (
+        T >= 1
+        and 1 <= top_k <= MOE_ROUTED_MAX_TOPK
+        and hidden > 0
+        and hidden % 128 == 0
+        and inter > 0
+        and inter % 64 == 0
+    )
+
+
+def moe_routed_prefill_mlp(
+    x: torch.Tensor,
+    topi: torch.Tensor,
+    topw: torch.Tensor,
+    w_gate_up: torch.Tensor,
+    w_down: torch.Tensor,
+    expert_lo: int = 0,
+) -> torch.Tensor:
+    """Routed mixture-of-experts SwiGLU MLP for prefill-sized batches, bf16
+    experts: the contract of ``moe_routed_mlp`` (same tensors, global expert
+    ids, pairs outside [expert_lo, expert_lo + E_local) contribute nothing,
+    act rounded to bf16 once, f32 accumulation, output rounded once) for any
+    T >= 1, up to 256 local experts and top-k <= 8, on MFMA grouped GEMMs
+    that stage W and X tiles through LDS (csrc/moe_prefill.hip). No host
+    synchronisation; grids depend on shapes only. Bit-identical from run to
+    run, and permuting the rows of the batch permutes the output rows bit for
+    bit; not bit-equal to ``moe_routed_mlp``."""
+    if not x.is_cuda:
+        return torch_ref.moe_routed_mlp(
+            x, topi, topw, w_gate_up, w_down, expert_lo
+        )
+    C = _native("moe_routed_prefill_mlp")
+    T, H = x.shape
+    k = topi.shape[1]
+    E, _, inter = w_down.shape
+    dev = x.device
+    chunk = min(T, MOE_PREFILL_CHUNK_TOKENS)
+    out = torch.empty_like(x)
+    topw = topw.float()
+    ws = torch.empty(
+        C.moe_prefill_ws_ints(chunk, k, E), dtype=torch.int32, device=dev
+    )
+    act = torch.empty((chunk * k, inter), dtype=x.dtype, device=dev)
+    y = torch.empty((chunk * k, H), dtype=torch.float32, device=dev)
+    for t0 in range(0, T, chunk):
+        t1 = min(T, t0 + chunk)
+        C.moe_routed_prefill_mlp(
+            out[t0:t1], x[t0:t1], topi[t0:t1], topw[t0:t1], w_gate_up,
+            w_down, int(expert_lo), ws, act, y, int(MOE_PREFILL_ROW_FAST),
+        )
+    return out
+
+
 # -- KV export / import (prefill-decode disaggregation) ----------------------
 
 # device table of the 2L cache base pointers (K0, V0, K1, V1, ...), built the

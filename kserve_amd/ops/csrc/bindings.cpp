@@ -93,6 +93,12 @@ hipError_t ks_moe_routed_mlp_w4(void*, const void*, const void*, const void*,
                                 const void*, const void*, const void*,
                                 const void*, void*, void*, void*, void*, int,
                                 int, int, int, int, int, hipStream_t);
+int ks_moe_prefill_supported(int, int, int, int);
+long ks_moe_prefill_ws_ints(int, int, int);
+hipError_t ks_moe_routed_prefill_mlp(void*, const void*, const void*,
+                                     const void*, const void*, const void*,
+                                     void*, void*, void*, int, int, int, int,
+                                     int, int, int, hipStream_t);
 hipError_t ks_kv_gather_pages(void*, const void*, const void*, int, int, long,
                               int, int, int, int, hipStream_t);
 hipError_t ks_kv_scatter_pages(const void*, const void*, const void*, int, int,
@@ -864,6 +870,73 @@ void moe_routed_mlp_w4(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
             "moe_routed_mlp_w4");
 }
 
+bool moe_prefill_supported(int64_t T, int64_t k, int64_t H, int64_t I) {
+  const int64_t lim = 1 << 30;
+  return T >= 1 && T < lim && k >= 1 && k < lim && H >= 1 && H < lim &&
+         I >= 1 && I < lim &&
+         ks_moe_prefill_supported((int)T, (int)k, (int)H, (int)I) != 0;
+}
+
+int64_t moe_prefill_ws_ints(int64_t T, int64_t k, int64_t E) {
+  return ks_moe_prefill_ws_ints((int)T, (int)k, (int)E);
+}
+
+// Routed MoE MLP for prefill batches (csrc/moe_prefill.hip), bf16 experts:
+// the tensors of moe_routed_mlp, any T with T * k <= 65536. The workspaces
+// may be larger than this call needs (ops.moe_routed_prefill_mlp reuses them
+// across its chunks): ws int32 [>= moe_prefill_ws_ints(T, k, E)], act bf16
+// [>= T * k * I], y f32 [>= T * k * H].
+void moe_routed_prefill_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+                            at::Tensor& topw, at::Tensor& w_gate_up,
+                            at::Tensor& w_down, int64_t expert_lo,
+                            at::Tensor& ws, at::Tensor& act, at::Tensor& y,
+                            int64_t row_fast) {
+  CHECK_BF16_CONTIG(out);
+  CHECK_BF16_CONTIG(x);
+  CHECK_BF16_CONTIG(act);
+  CHECK_BF16_CONTIG(w_gate_up);
+  CHECK_BF16_CONTIG(w_down);
+  TORCH_CHECK(x.dim() == 2 && w_gate_up.dim() == 3 && w_down.dim() == 3 &&
+                  topi.dim() == 2,
+              "moe_routed_prefill_mlp: x [T, H], topi [T, k], w_gate_up "
+              "[E, 2I, H], w_down [E, H, I]");
+  const int64_t T = x.size(0), H = x.size(1), k = topi.size(1);
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  TORCH_CHECK(moe_prefill_supported(T, k, H, I),
+              "moe_routed_prefill_mlp needs T >= 1, top-k <= 8, T * k <= "
+              "65536, H % 128 == 0 and I % 64 == 0");
+  TORCH_CHECK(E >= 1 && E <= 256,
+              "moe_routed_prefill_mlp needs <= 256 local experts");
+  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) == H &&
+                  w_down.size(0) == E && w_down.size(1) == H,
+              "moe_routed_prefill_mlp: expert weight shapes disagree");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == T && out.size(1) == H,
+              "out must be [T, H]");
+  TORCH_CHECK(topi.scalar_type() == at::kLong && topi.is_cuda() &&
+                  topi.is_contiguous() && topi.size(0) == T,
+              "topi must be a contiguous int64 [T, k] GPU tensor");
+  TORCH_CHECK(topw.scalar_type() == at::kFloat && topw.is_cuda() &&
+                  topw.is_contiguous() && topw.sizes() == topi.sizes(),
+              "topw must be a contiguous f32 [T, k] GPU tensor");
+  TORCH_CHECK(expert_lo >= 0 && expert_lo < (1 << 30),
+              "expert_lo out of range");
+  TORCH_CHECK(ws.scalar_type() == at::kInt && ws.is_cuda() &&
+                  ws.is_contiguous() &&
+                  ws.numel() >= moe_prefill_ws_ints(T, k, E),
+              "ws must be int32 [>= moe_prefill_ws_ints(T, k, E)]");
+  TORCH_CHECK(act.numel() >= T * k * I, "act must be bf16 [>= T * k * I]");
+  TORCH_CHECK(y.scalar_type() == at::kFloat && y.is_cuda() &&
+                  y.is_contiguous() && y.numel() >= T * k * H,
+              "y must be f32 [>= T * k * H]");
+  check_hip(ks_moe_routed_prefill_mlp(
+                out.data_ptr(), x.data_ptr(), topi.data_ptr(),
+                topw.data_ptr(), w_gate_up.data_ptr(), w_down.data_ptr(),
+                ws.data_ptr(), act.data_ptr(), y.data_ptr(), (int)T, (int)k,
+                (int)H, (int)I, (int)E, (int)expert_lo, row_fast != 0,
+                current_stream()),
+            "moe_routed_prefill_mlp");
+}
+
 // Shared checks of the KV export/import ops. `caches` is K0, V0, K1, V1, ...
 // and `bases` the device table of their base pointers in the same order
 // (built once by the caller); returns the bytes of one page of one tensor.
@@ -1024,6 +1097,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "routed MoE SwiGLU MLP, fp8 e4m3 expert weights (per-row f32 scales)");
   m.def("moe_routed_mlp_w4", &moe_routed_mlp_w4,
         "routed MoE SwiGLU MLP, MXFP4 expert weights (E8M0 block scales)");
+  m.def("moe_prefill_ws_ints", &moe_prefill_ws_ints,
+        "int32 workspace elements of moe_routed_prefill_mlp (T, top-k, E)");
+  m.def("moe_routed_prefill_mlp", &moe_routed_prefill_mlp,
+        "routed MoE SwiGLU MLP for prefill batches (grouped MFMA GEMMs, W "
+        "and X through LDS)");
   m.def("kv_gather_pages", &kv_gather_pages,
         "gather a request's KV pages of every layer into one buffer");
   m.def("kv_scatter_pages", &kv_scatter_pages,

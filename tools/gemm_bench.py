@@ -6,6 +6,7 @@ Run on GPU: python tools/gemm_bench.py [--tune]
             python tools/gemm_bench.py --w8 [--out FILE.md]
             python tools/gemm_bench.py --w4 [--out FILE.md]
             python tools/gemm_bench.py --moe [--out FILE.md]
+            python tools/gemm_bench.py --moe-prefill [--out FILE.md]
 
 --w8 is the A/B behind ops.W8_MAX_TOKENS (profiles/w8_gemm.md): per
 Llama-3-8B projection shape and token batch it times, in one process and
@@ -20,6 +21,10 @@ the columns (a) ops.linear on bf16 weights, (b) the fp8-weight skinny GEMM,
 --moe is the A/B behind MixtralMoE.ROUTED_MAX_TOKENS (profiles/
 moe_routed.md): one Mixtral-8x7B MoE layer per token batch, the routed
 grouped kernels (ops.moe_routed_mlp) against the dense-bmm path.
+
+--moe-prefill is the A/B behind MixtralMoE.ROUTED_PREFILL_MAX_TOKENS (same
+profile, "Prefill"): the same layer at prefill batches, the routed prefill
+kernels (ops.moe_routed_prefill_mlp) against the sparse per-expert loop.
 """
 
 import argparse
@@ -38,6 +43,9 @@ parser.add_argument("--w4", action="store_true",
 parser.add_argument("--moe", action="store_true",
                     help="routed MoE MLP against the dense-bmm path, one "
                          "Mixtral-8x7B layer (profiles/moe_routed.md)")
+parser.add_argument("--moe-prefill", action="store_true",
+                    help="routed MoE prefill MLP against the sparse loop, "
+                         "one Mixtral-8x7B layer (profiles/moe_routed.md)")
 parser.add_argument("--quantization", choices=("fp8", "mxfp4"), default=None,
                     help="--moe: the routed layer with experts in this "
                          "format against the routed bf16 layer")
@@ -504,6 +512,112 @@ def bench_moe_quant(q):
             f.write("\n".join(lines) + "\n")
 
 
+def bench_moe_prefill():
+    """One Mixtral-8x7B MoE layer (H 4096, I 14336, E 8, k 2) at prefill
+    batches: ops.moe_routed_prefill_mlp, in both grid orders, against
+    MixtralMoE._forward_sparse on the same inputs. The method is bench_moe's:
+    the variants alternate inside every round, device events around calls
+    that end in a synchronise, median and spread of 5 rounds after a warm-up
+    round. TFLOP/s from the routed pairs' 2 * T*k * 3*H*I, share of the
+    2.5 PFLOP/s dense bf16 peak; times are whole calls (align, GEMMs,
+    combine, workspace allocations; for the sparse loop its host
+    synchronisations too). The check is the test allowance around the sparse
+    result. The last row routes every token to the same two experts."""
+    import statistics
+
+    from kserve_amd import ops
+    from kserve_amd.engine.config import ModelConfig
+    from kserve_amd.models.llama import MixtralMoE
+
+    H, I, E, k = 4096, 14336, 8, 2
+    PEAK_FLOPS = 2.5e15
+    rounds = 5
+    with torch.device(dev):
+        moe = MixtralMoE(ModelConfig.mixtral_8x7b(), dtype=torch.bfloat16)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    moe.w_gate_up.data.normal_(0, H ** -0.5, generator=gen)
+    moe.w_down.data.normal_(0, I ** -0.5, generator=gen)
+
+    def timed(fn, iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(iters):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / iters * 1000
+
+    lines = [
+        "| T | routing | sparse us | spread | feature-fastest us | spread "
+        "| row-fastest us | spread | sparse/best | best TFLOP/s | % of peak "
+        "| max diff / allowance |",
+        "|---|---|---|---|---|---|---|---|---|---|---|---|",
+    ]
+    print(lines[0]); print(lines[1])
+    cases = [(T, "uniform") for T in (512, 1024, 2048, 4096, 8192)]
+    for T, mode in cases + [(2048, "two experts")]:
+        x = torch.randn(T, H, dtype=torch.bfloat16, device=dev, generator=gen)
+        logits = torch.randn(T, E, device=dev, generator=gen)
+        topw, topi = torch.softmax(logits, -1).topk(k, -1)
+        topw = topw / topw.sum(-1, keepdim=True)
+        if mode != "uniform":
+            topi = topi[:1].expand(T, k).contiguous()
+
+        def fs():
+            return moe._forward_sparse(x, topi, topw)
+
+        def fr(row_fast):
+            ops.MOE_PREFILL_ROW_FAST = row_fast
+            return ops.moe_routed_prefill_mlp(
+                x, topi, topw, moe.w_gate_up, moe.w_down, 0
+            )
+
+        variants = (("s", fs), ("f", lambda: fr(False)), ("r", lambda: fr(True)))
+        iters = max(2, min(20, 16384 // T))  # >= 40 ms per window
+        res = {key: [] for key, _ in variants}
+        for r in range(rounds + 1):  # round 0 is warm-up
+            for key, fn in variants:
+                t = timed(fn, iters)
+                if r:
+                    res[key].append(t)
+        med = {key: statistics.median(v) for key, v in res.items()}
+        spread = {key: (max(v) - min(v)) / med[key] for key, v in res.items()}
+        best = min(med["f"], med["r"])
+        flops = 2 * T * k * 3 * H * I
+        # allowance around the sparse result, |act| @ |w_down| per routed pair
+        ref = fs().float()
+        allow = torch.zeros_like(ref)
+        for e in range(E):
+            t_idx, j_idx = (topi == e).nonzero(as_tuple=True)
+            if t_idx.numel() == 0:
+                continue
+            act = ops.silu_and_mul(x[t_idx] @ moe.w_gate_up[e].t()).float()
+            allow.index_add_(
+                0, t_idx,
+                (act.abs() @ moe.w_down[e].float().abs().t())
+                * topw[t_idx, j_idx].unsqueeze(1),
+            )
+        allow = 2.0 ** -8 * ref.abs() + (2.0 ** -8 + (H + I) * 2.0 ** -23) * allow
+        ratio = ((fr(False).float() - ref).abs() / allow).max().item()
+        line = (
+            f"| {T} | {mode} | {med['s']:.0f} | {spread['s']:.1%} "
+            f"| {med['f']:.0f} | {spread['f']:.1%} | {med['r']:.0f} "
+            f"| {spread['r']:.1%} | {med['s'] / best:.2f} "
+            f"| {flops / best / 1e6:.0f} | {flops / PEAK_FLOPS * 1e6 / best:.0%} "
+            f"| {ratio:.3f} |"
+        )
+        print(line, flush=True)
+        lines.append(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if args.moe_prefill:
+    bench_moe_prefill()
+    sys.exit(0)
 if args.moe:
     if args.quantization:
         bench_moe_quant(args.quantization)
