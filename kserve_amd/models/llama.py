@@ -395,8 +395,9 @@ class MixtralMoE(nn.Module):
 
     def _forward_sparse(self, x, topi, topw):
         """Token-bucketed loop (prefill): exact FLOPs, host-side gather.
-        With quantized experts it is also the only path beside the routed
-        kernel (CPU, non-bf16 activations, T > ROUTED_MAX_TOKENS)."""
+        With quantized experts it is the only path beside the routed decode
+        and prefill kernels: CPU, non-bf16 activations, shapes those kernels
+        do not take, and T above ROUTED_PREFILL_MAX_TOKENS of the format."""
         T = x.shape[0]
         out = torch.zeros_like(x)
         flat_i = topi.flatten()
@@ -443,24 +444,29 @@ class MixtralMoE(nn.Module):
 
     # Batches the routed prefill kernels (ops.moe_routed_prefill_mlp) take
     # over from the sparse loop: ROUTED_MAX_TOKENS < T <=
-    # ROUTED_PREFILL_MAX_TOKENS, bf16 experts. On a Mixtral-8x7B layer they
-    # are 2.15x / 1.65x / 1.30x the sparse loop at 512 / 1024 / 2048 tokens
-    # and 0.94x / 0.76x at 4096 / 8192, where the per-expert library GEMMs
-    # are large enough to win (profiles/moe_routed.md, "Prefill").
-    ROUTED_PREFILL_MAX_TOKENS = 2048
+    # ROUTED_PREFILL_MAX_TOKENS[quantization]. bf16 experts: on a
+    # Mixtral-8x7B layer they are 2.15x / 1.65x / 1.30x the sparse loop at
+    # 512 / 1024 / 2048 tokens and 0.94x / 0.76x at 4096 / 8192, where the
+    # per-expert library GEMMs are large enough to win. Quantized experts:
+    # the sparse loop also dequantizes every expert it visits, see
+    # profiles/moe_routed.md, "Prefill" and "Quantized prefill".
+    ROUTED_PREFILL_MAX_TOKENS = {None: 2048, "fp8": 8192, "mxfp4": 8192}
 
     def _use_routed_prefill(self, x: torch.Tensor) -> bool:
         return (
             self.moe_kernel == "routed"
             and x.is_cuda
             and x.dtype == torch.bfloat16
-            and self.weight_format is None
-            and self.w_gate_up.dtype == torch.bfloat16
+            and (
+                self.weight_format is not None
+                or self.w_gate_up.dtype == torch.bfloat16
+            )
             and self.ROUTED_MAX_TOKENS < x.shape[0]
-            <= self.ROUTED_PREFILL_MAX_TOKENS
+            <= self.ROUTED_PREFILL_MAX_TOKENS[self.quantization]
             and self.experts_per_rank <= 256
             and ops.moe_routed_prefill_supported(
-                x.shape[0], self.top_k, x.shape[1], self.inter_local
+                x.shape[0], self.top_k, x.shape[1], self.inter_local,
+                self.quantization,
             )
         )
 
@@ -486,9 +492,17 @@ class MixtralMoE(nn.Module):
                     quantization=self.quantization,
                 )
         elif self._use_routed_prefill(x):
-            out = ops.moe_routed_prefill_mlp(
-                x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo
-            )
+            if self.weight_format is None:
+                out = ops.moe_routed_prefill_mlp(
+                    x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo
+                )
+            else:
+                out = ops.moe_routed_prefill_mlp(
+                    x, topi, topw, self.w_gate_up, self.w_down, self.expert_lo,
+                    gate_up_scale=self.w_gate_up_scale,
+                    down_scale=self.w_down_scale,
+                    quantization=self.quantization,
+                )
         elif self.weight_format is not None:
             # no quantized dense-bmm path
             out = self._forward_sparse(x, topi, topw)

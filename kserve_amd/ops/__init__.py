@@ -779,12 +779,23 @@ MOE_PREFILL_CHUNK_TOKENS = 2048
 MOE_PREFILL_ROW_FAST = False
 
 
+_MOE_PREFILL_BINDING = {
+    "fp8": "moe_routed_prefill_mlp_w8", "mxfp4": "moe_routed_prefill_mlp_w4",
+}
+
+
 def moe_routed_prefill_supported(
-    T: int, top_k: int, hidden: int, inter: int
+    T: int, top_k: int, hidden: int, inter: int,
+    quantization: Optional[str] = None,
 ) -> bool:
     """Shapes ops.moe_routed_prefill_mlp takes (dtype and device aside): any
     T >= 1 (batches above MOE_PREFILL_CHUNK_TOKENS run in chunks), top-k <= 8,
-    hidden % 128 == 0 and inter % 64 == 0."""
+    hidden % 128 == 0 and inter % 64 == 0, the same for bf16 experts and for
+    every ``quantization`` (the K step is 64 in each format)."""
+    if quantization is not None:
+        from kserve_amd.ops import quant
+
+        quant.check_quantization(quantization)
     return (
         T >= 1
         and 1 <= top_k <= MOE_ROUTED_MAX_TOPK
@@ -802,24 +813,43 @@ def moe_routed_prefill_mlp(
     w_gate_up: torch.Tensor,
     w_down: torch.Tensor,
     expert_lo: int = 0,
+    gate_up_scale: Optional[torch.Tensor] = None,
+    down_scale: Optional[torch.Tensor] = None,
+    quantization: Optional[str] = None,
 ) -> torch.Tensor:
-    """Routed mixture-of-experts SwiGLU MLP for prefill-sized batches, bf16
-    experts: the contract of ``moe_routed_mlp`` (same tensors, global expert
-    ids, pairs outside [expert_lo, expert_lo + E_local) contribute nothing,
-    act rounded to bf16 once, f32 accumulation, output rounded once) for any
-    T >= 1, up to 256 local experts and top-k <= 8, on MFMA grouped GEMMs
-    that stage W and X tiles through LDS (csrc/moe_prefill.hip). No host
-    synchronisation; grids depend on shapes only. Bit-identical from run to
-    run, and permuting the rows of the batch permutes the output rows bit for
-    bit; not bit-equal to ``moe_routed_mlp``."""
+    """Routed mixture-of-experts SwiGLU MLP for prefill-sized batches: the
+    contract of ``moe_routed_mlp`` (same tensors, global expert ids, pairs
+    outside [expert_lo, expert_lo + E_local) contribute nothing, act rounded
+    to bf16 once, f32 accumulation, output rounded once; ``quantization``,
+    ``gate_up_scale`` and ``down_scale`` as there, the experts then being
+    fp8 or MXFP4 codes) for any T >= 1, up to 256 local experts and
+    top-k <= 8, on MFMA grouped GEMMs that stage W and X tiles through LDS
+    (csrc/moe_prefill.hip); quantized W stays codes down to the MFMA operand.
+    No host synchronisation; grids depend on shapes only. Bit-identical from
+    run to run, and permuting the rows of the batch permutes the output rows
+    bit for bit; not bit-equal to ``moe_routed_mlp``."""
+    fmt = None
+    if quantization is not None:
+        from kserve_amd.ops import quant
+
+        quant.check_quantization(quantization)
+        fmt = quant.WEIGHT_FORMATS[quantization]
+        if gate_up_scale is None or down_scale is None:
+            raise ValueError(
+                f"quantization={quantization!r} needs gate_up_scale and "
+                "down_scale"
+            )
     if not x.is_cuda:
         return torch_ref.moe_routed_mlp(
-            x, topi, topw, w_gate_up, w_down, expert_lo
+            x, topi, topw, w_gate_up, w_down, expert_lo,
+            gate_up_scale=gate_up_scale, down_scale=down_scale,
+            quantization=quantization,
         )
     C = _native("moe_routed_prefill_mlp")
     T, H = x.shape
     k = topi.shape[1]
-    E, _, inter = w_down.shape
+    E = w_down.shape[0]
+    inter = w_down.shape[2] * (fmt.per_byte if fmt else 1)
     dev = x.device
     chunk = min(T, MOE_PREFILL_CHUNK_TOKENS)
     out = torch.empty_like(x)
@@ -831,10 +861,14 @@ def moe_routed_prefill_mlp(
     y = torch.empty((chunk * k, H), dtype=torch.float32, device=dev)
     for t0 in range(0, T, chunk):
         t1 = min(T, t0 + chunk)
-        C.moe_routed_prefill_mlp(
-            out[t0:t1], x[t0:t1], topi[t0:t1], topw[t0:t1], w_gate_up,
-            w_down, int(expert_lo), ws, act, y, int(MOE_PREFILL_ROW_FAST),
-        )
+        rows = (out[t0:t1], x[t0:t1], topi[t0:t1], topw[t0:t1])
+        rest = (int(expert_lo), ws, act, y, int(MOE_PREFILL_ROW_FAST))
+        if fmt is None:
+            C.moe_routed_prefill_mlp(*rows, w_gate_up, w_down, *rest)
+        else:
+            getattr(C, _MOE_PREFILL_BINDING[quantization])(
+                *rows, w_gate_up, gate_up_scale, w_down, down_scale, *rest
+            )
     return out
 
 

@@ -97,8 +97,9 @@ int ks_moe_prefill_supported(int, int, int, int);
 long ks_moe_prefill_ws_ints(int, int, int);
 hipError_t ks_moe_routed_prefill_mlp(void*, const void*, const void*,
                                      const void*, const void*, const void*,
-                                     void*, void*, void*, int, int, int, int,
-                                     int, int, int, hipStream_t);
+                                     const void*, const void*, int, void*,
+                                     void*, void*, int, int, int, int, int,
+                                     int, int, hipStream_t);
 hipError_t ks_kv_gather_pages(void*, const void*, const void*, int, int, long,
                               int, int, int, int, hipStream_t);
 hipError_t ks_kv_scatter_pages(const void*, const void*, const void*, int, int,
@@ -881,33 +882,41 @@ int64_t moe_prefill_ws_ints(int64_t T, int64_t k, int64_t E) {
   return ks_moe_prefill_ws_ints((int)T, (int)k, (int)E);
 }
 
-// Routed MoE MLP for prefill batches (csrc/moe_prefill.hip), bf16 experts:
-// the tensors of moe_routed_mlp, any T with T * k <= 65536. The workspaces
-// may be larger than this call needs (ops.moe_routed_prefill_mlp reuses them
-// across its chunks): ws int32 [>= moe_prefill_ws_ints(T, k, E)], act bf16
+// Routed MoE MLP for prefill batches (csrc/moe_prefill.hip): the tensors of
+// moe_routed_mlp and its _w8 / _w4 forms, any T with T * k <= 65536. wformat
+// is the kernel's (0 bf16, 1 fp8, 2 MXFP4), per_el the logical weights per
+// code element; the scales are null for bf16. The workspaces may be larger
+// than this call needs (ops.moe_routed_prefill_mlp reuses them across its
+// chunks): ws int32 [>= moe_prefill_ws_ints(T, k, E)], act bf16
 // [>= T * k * I], y f32 [>= T * k * H].
-void moe_routed_prefill_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
-                            at::Tensor& topw, at::Tensor& w_gate_up,
-                            at::Tensor& w_down, int64_t expert_lo,
-                            at::Tensor& ws, at::Tensor& act, at::Tensor& y,
-                            int64_t row_fast) {
+void moe_prefill_run(int wformat, int per_el, at::ScalarType code_type,
+                     at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+                     at::Tensor& topw, at::Tensor& w_gate_up,
+                     at::Tensor& w_down, const at::Tensor* gate_up_scale,
+                     const at::Tensor* down_scale, int64_t expert_lo,
+                     at::Tensor& ws, at::Tensor& act, at::Tensor& y,
+                     int64_t row_fast) {
   CHECK_BF16_CONTIG(out);
   CHECK_BF16_CONTIG(x);
   CHECK_BF16_CONTIG(act);
-  CHECK_BF16_CONTIG(w_gate_up);
-  CHECK_BF16_CONTIG(w_down);
+  TORCH_CHECK(w_gate_up.is_cuda() && w_gate_up.is_contiguous() &&
+                  w_down.is_cuda() && w_down.is_contiguous() &&
+                  w_gate_up.scalar_type() == code_type &&
+                  w_down.scalar_type() == code_type,
+              "moe_routed_prefill_mlp: expert weights must be contiguous ",
+              code_type, " GPU tensors");
   TORCH_CHECK(x.dim() == 2 && w_gate_up.dim() == 3 && w_down.dim() == 3 &&
                   topi.dim() == 2,
               "moe_routed_prefill_mlp: x [T, H], topi [T, k], w_gate_up "
               "[E, 2I, H], w_down [E, H, I]");
   const int64_t T = x.size(0), H = x.size(1), k = topi.size(1);
-  const int64_t E = w_gate_up.size(0), I = w_down.size(2);
+  const int64_t E = w_gate_up.size(0), I = w_down.size(2) * per_el;
   TORCH_CHECK(moe_prefill_supported(T, k, H, I),
               "moe_routed_prefill_mlp needs T >= 1, top-k <= 8, T * k <= "
               "65536, H % 128 == 0 and I % 64 == 0");
   TORCH_CHECK(E >= 1 && E <= 256,
               "moe_routed_prefill_mlp needs <= 256 local experts");
-  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) == H &&
+  TORCH_CHECK(w_gate_up.size(1) == 2 * I && w_gate_up.size(2) * per_el == H &&
                   w_down.size(0) == E && w_down.size(1) == H,
               "moe_routed_prefill_mlp: expert weight shapes disagree");
   TORCH_CHECK(out.dim() == 2 && out.size(0) == T && out.size(1) == H,
@@ -928,13 +937,66 @@ void moe_routed_prefill_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
   TORCH_CHECK(y.scalar_type() == at::kFloat && y.is_cuda() &&
                   y.is_contiguous() && y.numel() >= T * k * H,
               "y must be f32 [>= T * k * H]");
+  if (wformat == 1) {  // one f32 scale per output row
+    check_moe_scale("gate_up_scale", *gate_up_scale, at::kFloat, {E, 2 * I});
+    check_moe_scale("down_scale", *down_scale, at::kFloat, {E, H});
+  } else if (wformat == 2) {  // one E8M0 byte per row and 32 inputs
+    check_moe_scale("gate_up_scale", *gate_up_scale, at::kByte,
+                    {E, 2 * I, H / 32});
+    check_moe_scale("down_scale", *down_scale, at::kByte, {E, H, I / 32});
+  }
+  auto aligned16 = [](const at::Tensor* t) {
+    return t == nullptr || ((uintptr_t)t->data_ptr() & 15) == 0;
+  };
+  TORCH_CHECK(aligned16(&w_gate_up) && aligned16(&w_down) &&
+                  aligned16(gate_up_scale) && aligned16(down_scale),
+              "moe_routed_prefill_mlp: expert weights and scales must be "
+              "16-byte aligned");
   check_hip(ks_moe_routed_prefill_mlp(
                 out.data_ptr(), x.data_ptr(), topi.data_ptr(),
                 topw.data_ptr(), w_gate_up.data_ptr(), w_down.data_ptr(),
+                gate_up_scale ? gate_up_scale->data_ptr() : nullptr,
+                down_scale ? down_scale->data_ptr() : nullptr, wformat,
                 ws.data_ptr(), act.data_ptr(), y.data_ptr(), (int)T, (int)k,
                 (int)H, (int)I, (int)E, (int)expert_lo, row_fast != 0,
                 current_stream()),
             "moe_routed_prefill_mlp");
+}
+
+void moe_routed_prefill_mlp(at::Tensor& out, at::Tensor& x, at::Tensor& topi,
+                            at::Tensor& topw, at::Tensor& w_gate_up,
+                            at::Tensor& w_down, int64_t expert_lo,
+                            at::Tensor& ws, at::Tensor& act, at::Tensor& y,
+                            int64_t row_fast) {
+  moe_prefill_run(0, 1, at::kBFloat16, out, x, topi, topw, w_gate_up, w_down,
+                  nullptr, nullptr, expert_lo, ws, act, y, row_fast);
+}
+
+// fp8 experts: codes e4m3 [E, 2I, H] / [E, H, I], f32 scales [E, 2I] / [E, H]
+void moe_routed_prefill_mlp_w8(at::Tensor& out, at::Tensor& x,
+                               at::Tensor& topi, at::Tensor& topw,
+                               at::Tensor& w_gate_up,
+                               at::Tensor& gate_up_scale, at::Tensor& w_down,
+                               at::Tensor& down_scale, int64_t expert_lo,
+                               at::Tensor& ws, at::Tensor& act, at::Tensor& y,
+                               int64_t row_fast) {
+  moe_prefill_run(1, 1, at::kFloat8_e4m3fn, out, x, topi, topw, w_gate_up,
+                  w_down, &gate_up_scale, &down_scale, expert_lo, ws, act, y,
+                  row_fast);
+}
+
+// MXFP4 experts: codes uint8 [E, 2I, H/2] / [E, H, I/2], E8M0 scales uint8
+// [E, 2I, H/32] / [E, H, I/32]
+void moe_routed_prefill_mlp_w4(at::Tensor& out, at::Tensor& x,
+                               at::Tensor& topi, at::Tensor& topw,
+                               at::Tensor& w_gate_up,
+                               at::Tensor& gate_up_scale, at::Tensor& w_down,
+                               at::Tensor& down_scale, int64_t expert_lo,
+                               at::Tensor& ws, at::Tensor& act, at::Tensor& y,
+                               int64_t row_fast) {
+  moe_prefill_run(2, 2, at::kByte, out, x, topi, topw, w_gate_up, w_down,
+                  &gate_up_scale, &down_scale, expert_lo, ws, act, y,
+                  row_fast);
 }
 
 // Shared checks of the KV export/import ops. `caches` is K0, V0, K1, V1, ...
@@ -1102,6 +1164,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_routed_prefill_mlp", &moe_routed_prefill_mlp,
         "routed MoE SwiGLU MLP for prefill batches (grouped MFMA GEMMs, W "
         "and X through LDS)");
+  m.def("moe_routed_prefill_mlp_w8", &moe_routed_prefill_mlp_w8,
+        "routed MoE prefill MLP, fp8 experts with per-row f32 scales");
+  m.def("moe_routed_prefill_mlp_w4", &moe_routed_prefill_mlp_w4,
+        "routed MoE prefill MLP, MXFP4 experts with E8M0 block scales");
   m.def("kv_gather_pages", &kv_gather_pages,
         "gather a request's KV pages of every layer into one buffer");
   m.def("kv_scatter_pages", &kv_scatter_pages,

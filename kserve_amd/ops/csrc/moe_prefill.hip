@@ -48,12 +48,46 @@
 // those sources: tile row -> sorted position -> pair -> token (pair / k).
 // Rows past the tile's count clamp to its last row; their results are never
 // stored, and row fragments wholly past the count skip their MFMAs
-// wave-uniformly. Another weight format would replace the W half of stage()
-// and the fragment read; nothing else knows how W is stored.
+// wave-uniformly. Only the W half of stage() and the W fragment read know how
+// W is stored.
 //
 // K loop: stage step kt + 1, wait (counted vmcnt) for step kt, barrier,
 // 16 ds_read_b128 + 32 MFMAs, barrier. The fences stay: the compiler does
 // not see the LDS writes of global_load_lds.
+//
+// Quantized experts (weight-only fp8 and MXFP4, kserve_amd/ops/quant.py, the
+// storage moe.hip takes): the GEMM kernel is a template over the weight
+// format (PfBf16, PfFp8, PfMxfp4 below). X, act, the accumulators, the tile
+// structure and BK = 64 do not change. W crosses HBM, L2 and LDS as codes: the
+// W tile of a step is 128 rows of 64 B (fp8, 8 KB, 2 staging instructions per
+// wave) or 32 B (MXFP4, 4 KB, 1 instruction). The operand layout stays: a
+// lane holds 8 consecutive K of one W row, now 8 or 4 bytes, read from LDS
+// with one ds_read_b64 / b32 and converted there (exactly) by the Fp8 / Mxfp4
+// converts of wq_formats.h.
+//
+// W swizzle for those rows (wswz): a row has 4 (fp8) or 2 (MXFP4) granules of
+// 16 B, and 256 B, one turn of the 64 banks, hold 4 or 8 rows; rows 4 or 8
+// apart would meet on the same banks. The granule index is XORed with the
+// next row bits, (row >> 2) & 3 or (row >> 3) & 1, which are offset bits 8..
+// in both layouts. fp8: the 32 lanes that read one logical granule pair (16
+// rows x 2 halves of a granule) then cover 16 distinct 16 B slots x 2 halves,
+// every bank once. MXFP4: the 64 lanes (16 rows x 4 dwords of one granule)
+// cover 8 rows x 8 dwords, every bank once. Derived for 64 banks of 4 B, not
+// measured. Like the X swizzle it lives in the per-lane source address.
+//
+// Scales. fp8: one f32 per W row; the epilogue loads the scales of a lane's 4
+// features per fragment (16 B) and multiplies the f32 accumulators, gate and
+// up before SiLU*mul, down before topw. MXFP4: one E8M0 byte per W row and 32
+// K, so one per row and MFMA K slice, two per row and step; the byte is the
+// scale operand of that slice's convert. The bytes go through LDS (see
+// stage()), requested with the step's tiles, one step ahead, and counted in
+// the same wait. Per step a wave issues NW = 4 + NIW + NSC loads (8 bf16,
+// 6 fp8, 6 MXFP4) and the vmcnt immediate is derived from NW.
+//
+// LDS: 64 KB bf16, 48 KB fp8, 42 KB MXFP4; the quantized kernels fit in 170
+// registers and run three workgroups per CU, which is what the freed LDS
+// buys (profiles/moe_routed.md, "Quantized prefill": 8-10% for fp8 against
+// two per CU, nothing for MXFP4).
 //
 // Grids depend on shapes only. The row-tile dimension is the static bound
 // min(cdiv(P, BM) + E, E * cdiv(T, BM)); a workgroup at or past the tile
@@ -68,6 +102,7 @@
 #include "common.h"
 #include "mfma_layouts.h"
 #include "skinny_shared.h"
+#include "wq_formats.h"
 
 #include <type_traits>
 
@@ -224,17 +259,74 @@ __device__ __forceinline__ int swz(int byte_off) {
   return byte_off ^ (((byte_off >> 8) & 15) << 4);
 }
 
+// ---- expert weight formats ----
+//
+// ROW_BYTES    bytes of one W row in a K step (BK elements)
+// STEP_SCALE   one E8M0 byte per W row and 32 K, applied in the convert
+// OUT_SCALE    one f32 scale per W row, applied to the accumulator
+// frag         the 8 bf16 of one MFMA from a lane's LDS read (raw_t)
+struct PfBf16 {
+  static constexpr int ROW_BYTES = 128;
+  static constexpr bool STEP_SCALE = false;
+  static constexpr bool OUT_SCALE = false;
+  using scale_t = float;  // unused
+  using raw_t = bf16x8_t;
+  static __device__ __forceinline__ bf16x8_t frag(const raw_t& r, float) {
+    return r;
+  }
+};
+
+struct PfFp8 {
+  static constexpr int ROW_BYTES = 64;
+  static constexpr bool STEP_SCALE = false;
+  static constexpr bool OUT_SCALE = true;
+  using scale_t = float;
+  typedef unsigned int raw_t __attribute__((ext_vector_type(2)));
+  static __device__ __forceinline__ bf16x8_t frag(const raw_t& r, float) {
+    return Fp8::cvt8(r[0], r[1]);
+  }
+};
+
+struct PfMxfp4 {
+  static constexpr int ROW_BYTES = 32;
+  static constexpr bool STEP_SCALE = true;
+  static constexpr bool OUT_SCALE = false;
+  using scale_t = unsigned char;
+  using raw_t = unsigned int;
+  static __device__ __forceinline__ bf16x8_t frag(const raw_t& r, float sc) {
+    return Mxfp4::cvt8(r, sc);
+  }
+};
+
+// Swizzle of the W tile, [128][ROW_BYTES]: bf16 rows are the X tile's. A
+// quantized row has ROW_BYTES / 16 granules (bits 4.. of the offset) and 256
+// bytes, one turn of the 64 banks, hold 256 / ROW_BYTES rows; the granule
+// index is XORed with the row bits from offset bit 8 up, the rows that would
+// land on the same banks. An involution, the key of a fragment's 16 rows
+// depends on the lane alone (16 rows are 1024 or 512 bytes, above the key).
+template <int ROW_BYTES>
+__device__ __forceinline__ int wswz(int byte_off) {
+  if constexpr (ROW_BYTES == 128) return swz(byte_off);
+  return byte_off ^ (((byte_off >> 8) & (ROW_BYTES / 16 - 1)) << 4);
+}
+
 // row_fast: blockIdx.x is the row tile and .y the feature block, else the
 // other way round
-template <bool GATE_UP>
+template <class Fmt, bool GATE_UP>
 __global__ __launch_bounds__(256) void moe_prefill_gemm_kernel(
     short* __restrict__ act_out,  // GATE_UP: [P][N] bf16 by sorted position
     float* __restrict__ y_out,    // !GATE_UP: [P][N] f32 by pair id
     const short* __restrict__ xin,  // GATE_UP: x [T][K]; else act [P][K]
-    const short* __restrict__ w,    // GATE_UP: [E][2N][K]; else [E][N][K]
+    // GATE_UP: [E][2N] rows, else [E][N] rows, of K * ROW_BYTES / BK bytes
+    const short* __restrict__ w,
+    // OUT_SCALE: f32 [E][2N] / [E][N]; STEP_SCALE: E8M0 [E][2N][K/32] /
+    // [E][N][K/32]; bf16: unused
+    const typename Fmt::scale_t* __restrict__ scale,
     const int* __restrict__ offsets, const int* __restrict__ sorted_pair,
     const int* __restrict__ tiles, const float* __restrict__ topw,  // [P]
     const int N, const int K, const int top_k, const int row_fast) {
+  constexpr int ROW_BYTES = Fmt::ROW_BYTES;
+  constexpr int W_TILE_BYTES = 128 * ROW_BYTES;
   const int tile = row_fast ? blockIdx.x : blockIdx.y;
   const int fb = row_fast ? blockIdx.y : blockIdx.x;
   if (tile >= tiles[0]) return;  // unused slot of the static grid
@@ -247,16 +339,28 @@ __global__ __launch_bounds__(256) void moe_prefill_gemm_kernel(
   const int wm = wave >> 1;  // rows wm * 64 + [0, 64)
   const int wn = wave & 1;   // W tile rows {0, 64} + wn * 32 + [0, 32)
 
-  // [buffer][0 = X tile, 1 = W tile]
-  __shared__ __attribute__((aligned(1024))) char lds[2][2][TILE_BYTES];
+  // [buffer][X tile, then W tile, then MXFP4 scales: 64 dwords per wave]
+  constexpr int SC_BYTES = Fmt::STEP_SCALE ? NWAVES * 256 : 0;
+  __shared__ __attribute__((aligned(1024))) char
+      lds[2][TILE_BYTES + W_TILE_BYTES + SC_BYTES];
+
+  // tile row of a W tile -> row of this expert's matrix
+  auto w_row_of = [&](const int r) {
+    return GATE_UP ? (r >> 6) * N + fb * FEAT_GATE_UP + (r & 63)
+                   : fb * FEAT_DOWN + r;
+  };
 
   // ---- per-lane staging sources, fixed over K ----
   // Instruction ii of this wave fills the linear KB `chunk` of a tile: lane
-  // writes LDS byte lin, which must hold tile byte swz(lin).
-  constexpr int NI = TILE_BYTES / 1024 / NWAVES;  // 4 per tile and wave
+  // writes LDS byte lin, which must hold tile byte swz(lin) (wswz for W).
+  constexpr int NI = TILE_BYTES / 1024 / NWAVES;     // X: 4 per wave
+  constexpr int NIW = W_TILE_BYTES / 1024 / NWAVES;  // W: 4, 2 or 1
+  // W offsets count shorts in every format: a row is K * WSH / BK of them
+  constexpr int WSH = ROW_BYTES / 2;
+  const int w_stride = K / BK * WSH;
   const short* w_e =
-      w + (long)e * (GATE_UP ? 2 : 1) * N * K;  // this expert's rows
-  int x_off[NI], w_off[NI];                     // elements
+      w + (long)e * (GATE_UP ? 2 : 1) * N * w_stride;  // this expert's rows
+  int x_off[NI], w_off[NIW];
 #pragma unroll
   for (int ii = 0; ii < NI; ++ii) {
     const int s = swz((wave + ii * NWAVES) * 1024 + lane * 16);
@@ -265,27 +369,64 @@ __global__ __launch_bounds__(256) void moe_prefill_gemm_kernel(
     const int pos = row_lo + min(r, rows - 1);
     const int src_row = GATE_UP ? sorted_pair[pos] / top_k : pos;
     x_off[ii] = src_row * K + col;
-    const int w_row = GATE_UP ? (r >> 6) * N + fb * FEAT_GATE_UP + (r & 63)
-                              : fb * FEAT_DOWN + r;
-    w_off[ii] = w_row * K + col;
   }
-  auto stage = [&](const int buf, const int k0) {
+#pragma unroll
+  for (int ii = 0; ii < NIW; ++ii) {
+    const int s = wswz<ROW_BYTES>((wave + ii * NWAVES) * 1024 + lane * 16);
+    w_off[ii] = w_row_of(s / ROW_BYTES) * w_stride + (s % ROW_BYTES) / 2;
+  }
+
+  // MXFP4 scales go through LDS like the tiles, one 4-byte global_load_lds
+  // per wave and step: lane l fetches the dword around the two E8M0 bytes
+  // (one per MFMA K slice) of this step for the wave's W row l, tile row
+  // wn * 32 + (l >> 5) * 64 + (l & 31). A row's bytes of a step start at an
+  // even offset, so the dword is that offset rounded down to 4 (the arrays
+  // are multiples of 4 bytes) and s_half says which half the step is in.
+  // Loaded straight to registers the bytes would be the only VM results the
+  // compiler tracks, and it then drains vmcnt to 0 before every second
+  // step's converts, which ends the prefetch; LDS costs 4 ds_read_b32.
+  int s_off = 0, s_half[4] = {0, 0, 0, 0};
+  const unsigned char* s_e = nullptr;
+  if constexpr (Fmt::STEP_SCALE) {
+    s_e = reinterpret_cast<const unsigned char*>(scale) +
+          (long)e * (GATE_UP ? 2 : 1) * N * (K / 32);
+    s_off = w_row_of(wn * 32 + (lane >> 5) * 64 + (lane & 31)) * (K / 32);
+#pragma unroll
+    for (int n = 0; n < 4; ++n)  // of the row this lane converts in fragment n
+      s_half[n] = (w_row_of(wn * 32 + (n >> 1) * 64 + (n & 1) * 16 +
+                            (lane & 15)) * (K / 32) >> 1) & 1;
+  }
+
+  auto stage = [&](const int buf, const int kt) {
+    const int k0 = kt * BK;
 #pragma unroll
     for (int ii = 0; ii < NI; ++ii)
       __builtin_amdgcn_global_load_lds(
           reinterpret_cast<const unsigned int*>(xin + x_off[ii] + k0),
           reinterpret_cast<unsigned int*>(
-              &lds[buf][0][(wave + ii * NWAVES) * 1024]),
+              &lds[buf][(wave + ii * NWAVES) * 1024]),
           16, 0, 0);
 #pragma unroll
-    for (int ii = 0; ii < NI; ++ii)
+    for (int ii = 0; ii < NIW; ++ii)
       __builtin_amdgcn_global_load_lds(
-          reinterpret_cast<const unsigned int*>(w_e + w_off[ii] + k0),
+          reinterpret_cast<const unsigned int*>(w_e + w_off[ii] + kt * WSH),
           reinterpret_cast<unsigned int*>(
-              &lds[buf][1][(wave + ii * NWAVES) * 1024]),
+              &lds[buf][TILE_BYTES + (wave + ii * NWAVES) * 1024]),
           16, 0, 0);
+    if constexpr (Fmt::STEP_SCALE)
+      __builtin_amdgcn_global_load_lds(
+          reinterpret_cast<const unsigned int*>(s_e +
+                                                ((s_off + kt * 2) & ~3)),
+          reinterpret_cast<unsigned int*>(
+              &lds[buf][TILE_BYTES + W_TILE_BYTES + wave * 256]),
+          4, 0, 0);
   };
-  constexpr int WAIT_NEXT = waitcnt_vmcnt(2 * NI);  // one step in flight
+  // Per step a wave issues NW VM operations: NI X and NIW W tile loads and
+  // NSC scale loads, all into LDS. Waiting for NW outstanding means the whole previous
+  // step has landed. A load added to stage() is added here.
+  constexpr int NSC = Fmt::STEP_SCALE ? 1 : 0;
+  constexpr int NW = NI + NIW + NSC;
+  constexpr int WAIT_NEXT = waitcnt_vmcnt(NW);  // one step in flight
   constexpr int WAIT_0 = waitcnt_vmcnt(0);
 
   // ---- fragment reads ----
@@ -301,6 +442,15 @@ __global__ __launch_bounds__(256) void moe_prefill_gemm_kernel(
       frag_lo[ks][par] = swz((par * 16 + (lane & 15)) * 128 +
                              (ks * 4 + (lane >> 4)) * 16) -
                          par * 16 * 128;
+  // Quantized W: lane reads ROW_BYTES / 8 bytes (its 8 K) of row base +
+  // (lane & 15) at byte ks * ROW_BYTES / 2 + (lane >> 4) * ROW_BYTES / 8.
+  // The key comes from lane & 15 alone, so one offset serves every base.
+  int wfrag_lo[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+    wfrag_lo[ks] = wswz<ROW_BYTES>((lane & 15) * ROW_BYTES +
+                                   ks * (ROW_BYTES / 2) +
+                                   (lane >> 4) * (ROW_BYTES / 8));
 
   f32x4_t acc[4][4];  // [row fragment m][W fragment n]
 #pragma unroll
@@ -314,16 +464,35 @@ __global__ __launch_bounds__(256) void moe_prefill_gemm_kernel(
   const int mact = __builtin_amdgcn_readfirstlane(
       max(0, min(4, (rows - wm * 64 + 15) >> 4)));
 
-  auto compute = [&](const int buf, auto full) {
-    const char* xt = &lds[buf][0][wm * 64 * 128];
-    const char* wt = &lds[buf][1][wn * 32 * 128];
+  auto compute = [&](const int buf, const int kt, auto full) {
+    const char* xt = &lds[buf][wm * 64 * 128];
+    const char* wt = &lds[buf][TILE_BYTES + wn * 32 * ROW_BYTES];
+    unsigned int sc2[4];  // MXFP4: the step's two E8M0 bytes of fragment n
+    if constexpr (Fmt::STEP_SCALE) {
+      const unsigned int* st = reinterpret_cast<const unsigned int*>(
+          &lds[buf][TILE_BYTES + W_TILE_BYTES + wave * 256]);
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+        sc2[n] = st[(n >> 1) * 32 + (n & 1) * 16 + (lane & 15)] >>
+                 (((s_half[n] + kt) & 1) * 16);
+    }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8_t wf[4], xf[4];
 #pragma unroll
-      for (int n = 0; n < 4; ++n)  // W tile row (n >> 1) * 64 + (n & 1) * 16
-        wf[n] = *reinterpret_cast<const bf16x8_t*>(
-            wt + ((n >> 1) * 64 + (n & 1) * 16) * 128 + frag_lo[ks][n & 1]);
+      for (int n = 0; n < 4; ++n) {  // W tile row (n >> 1) * 64 + (n & 1) * 16
+        const char* p = wt + ((n >> 1) * 64 + (n & 1) * 16) * ROW_BYTES;
+        if constexpr (ROW_BYTES == 128) {
+          wf[n] = *reinterpret_cast<const bf16x8_t*>(p + frag_lo[ks][n & 1]);
+        } else {  // the convert; MXFP4: with the E8M0 byte of K slice ks
+          float sc = 1.0f;
+          if constexpr (Fmt::STEP_SCALE)
+            sc = e8m0_to_float((sc2[n] >> (8 * ks)) & 0xffu);
+          wf[n] = Fmt::frag(*reinterpret_cast<const typename Fmt::raw_t*>(
+                                p + wfrag_lo[ks]),
+                            sc);
+        }
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m)
         xf[m] = *reinterpret_cast<const bf16x8_t*>(xt + m * 16 * 128 +
@@ -340,27 +509,47 @@ __global__ __launch_bounds__(256) void moe_prefill_gemm_kernel(
   };
 
   const int nk = K / BK;
+  auto step = [&](const int buf, const int kt, auto full) {
+    if (kt + 1 < nk) {
+      stage(buf ^ 1, kt + 1);
+      __builtin_amdgcn_s_waitcnt(WAIT_NEXT);  // step kt landed
+    } else {
+      __builtin_amdgcn_s_waitcnt(WAIT_0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();  // raw: no vmcnt drain (counted pipeline)
+    compute(buf, kt, full);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();  // readers done before lds[buf] is restaged
+  };
   auto k_loop = [&](auto full) {
     stage(0, 0);
-    for (int kt = 0; kt < nk; ++kt) {
-      const int buf = kt & 1;
-      if (kt + 1 < nk) {
-        stage(buf ^ 1, (kt + 1) * BK);
-        __builtin_amdgcn_s_waitcnt(WAIT_NEXT);  // step kt landed
-      } else {
-        __builtin_amdgcn_s_waitcnt(WAIT_0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();  // raw: no vmcnt drain (counted pipeline)
-      compute(buf, full);
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_barrier();  // readers done before lds[buf] is restaged
-    }
+    for (int kt = 0; kt < nk; ++kt) step(kt & 1, kt, full);
   };
   if (mact == 4) k_loop(std::true_type{});
   else k_loop(std::false_type{});
 
   // ---- epilogue: C row = feature (lane >> 4) * 4 + reg, col = tile row ----
+  // first feature of W fragment n (its tile row is the gate row in GATE_UP)
+  auto feat_of = [&](const int n) {
+    return GATE_UP
+               ? fb * FEAT_GATE_UP + wn * 32 + (n & 1) * 16 + ((lane >> 4) << 2)
+               : fb * FEAT_DOWN + (n >> 1) * 64 + wn * 32 + (n & 1) * 16 +
+                     ((lane >> 4) << 2);
+  };
+  // OUT_SCALE: the f32 scales of the lane's four features of every
+  // fragment, one 16 B load each, multiply the accumulators here, before
+  // SiLU*mul and before topw
+  if constexpr (Fmt::OUT_SCALE) {
+    const float* s_e = scale + (long)e * (GATE_UP ? 2 : 1) * N;
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+      const f32x4_t sc = *reinterpret_cast<const f32x4_t*>(
+          s_e + (GATE_UP ? (n >> 1) * N : 0) + feat_of(n));
+#pragma unroll
+      for (int m = 0; m < 4; ++m) acc[m][n] *= sc;
+    }
+  }
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     const int r = wm * 64 + m * 16 + (lane & 15);
@@ -435,6 +624,8 @@ extern "C" long ks_moe_prefill_ws_ints(int T, int top_k, int E) {
          (long)cdiv(P, ALIGN_BLOCK) * E + P;
 }
 
+namespace {
+
 // Workspaces (device): ws int32 [ks_moe_prefill_ws_ints], act bf16 [T*k][I],
 // y f32 [T*k][H]. Nothing needs clearing.
 //
@@ -442,14 +633,16 @@ extern "C" long ks_moe_prefill_ws_ints(int T, int top_k, int E) {
 // (the workgroups running together share one X tile and sweep the expert's
 // weights), 1 = row tile fastest (an expert's row tiles run together and
 // re-read one W tile from cache).
-extern "C" hipError_t ks_moe_routed_prefill_mlp(
+template <class Fmt>
+hipError_t moe_routed_prefill_mlp(
     void* out, const void* x, const void* topi, const void* topw,
-    const void* w_gate_up, const void* w_down, void* ws, void* act, void* y,
-    int T, int top_k, int H, int I, int E, int expert_lo, int row_fast,
-    hipStream_t stream) {
+    const void* w_gate_up, const void* w_down, const void* gate_up_scale,
+    const void* down_scale, void* ws, void* act, void* y, int T, int top_k,
+    int H, int I, int E, int expert_lo, int row_fast, hipStream_t stream) {
   if (!ks_moe_prefill_supported(T, top_k, H, I) || E < 1 || E > MAX_EXPERTS)
     return hipErrorInvalidValue;
-  // per-lane source offsets are 32-bit element counts
+  // per-lane source offsets are 32-bit counts of elements (X) or of shorts
+  // (W, never more than its elements)
   if ((long)T * H >= (1l << 31) || (long)T * top_k * I >= (1l << 31) ||
       2l * I * H >= (1l << 31))
     return hipErrorInvalidValue;
@@ -458,6 +651,13 @@ extern "C" hipError_t ks_moe_routed_prefill_mlp(
       ((uintptr_t)y & 15) != 0 || ((uintptr_t)out & 7) != 0 ||
       ((uintptr_t)ws & 3) != 0)
     return hipErrorInvalidValue;
+  // 16 B loads of f32 scales; E8M0 rows are K / 32 bytes, an even count
+  if ((Fmt::STEP_SCALE || Fmt::OUT_SCALE) &&
+      (gate_up_scale == nullptr || down_scale == nullptr ||
+       ((uintptr_t)gate_up_scale & 15) != 0 ||
+       ((uintptr_t)down_scale & 15) != 0))
+    return hipErrorInvalidValue;
+  using scale_t = typename Fmt::scale_t;
   const int P = T * top_k;
   const int nblk = cdiv(P, ALIGN_BLOCK);
   const int max_tiles = max_row_tiles(T, top_k, E);
@@ -476,19 +676,44 @@ extern "C" hipError_t ks_moe_routed_prefill_mlp(
   auto grid = [&](int nfb) {
     return row_fast ? dim3(max_tiles, nfb) : dim3(nfb, max_tiles);
   };
-  hipLaunchKernelGGL(moe_prefill_gemm_kernel<true>, grid(I / FEAT_GATE_UP),
-                     dim3(256), 0, stream, (short*)act, (float*)nullptr,
-                     (const short*)x, (const short*)w_gate_up, offsets,
-                     sorted_pair, tiles, (const float*)topw, I, H, top_k,
-                     row_fast);
-  hipLaunchKernelGGL(moe_prefill_gemm_kernel<false>, grid(H / FEAT_DOWN),
-                     dim3(256), 0, stream, (short*)nullptr, (float*)y,
-                     (const short*)act, (const short*)w_down, offsets,
-                     sorted_pair, tiles, (const float*)topw, H, I, top_k,
-                     row_fast);
+  hipLaunchKernelGGL((moe_prefill_gemm_kernel<Fmt, true>),
+                     grid(I / FEAT_GATE_UP), dim3(256), 0, stream, (short*)act,
+                     (float*)nullptr, (const short*)x, (const short*)w_gate_up,
+                     (const scale_t*)gate_up_scale, offsets, sorted_pair,
+                     tiles, (const float*)topw, I, H, top_k, row_fast);
+  hipLaunchKernelGGL((moe_prefill_gemm_kernel<Fmt, false>),
+                     grid(H / FEAT_DOWN), dim3(256), 0, stream, (short*)nullptr,
+                     (float*)y, (const short*)act, (const short*)w_down,
+                     (const scale_t*)down_scale, offsets, sorted_pair, tiles,
+                     (const float*)topw, H, I, top_k, row_fast);
   hipLaunchKernelGGL(prefill_combine_kernel, dim3(T, cdiv(H, 1024)),
                      dim3(256), 0, stream, (short*)out, (const float*)y,
                      (const long long*)topi, top_k, H, expert_lo, E);
   HIP_CHECK_KERNEL();
   return hipSuccess;
+}
+
+}  // namespace
+
+// wformat: 0 = bf16 experts (scales unused), 1 = fp8 codes [E][2I][H] /
+// [E][H][I] with f32 scales [E][2I] / [E][H], 2 = MXFP4 codes [E][2I][H/2] /
+// [E][H][I/2] with E8M0 scales [E][2I][H/32] / [E][H][I/32]
+extern "C" hipError_t ks_moe_routed_prefill_mlp(
+    void* out, const void* x, const void* topi, const void* topw,
+    const void* w_gate_up, const void* w_down, const void* gate_up_scale,
+    const void* down_scale, int wformat, void* ws, void* act, void* y, int T,
+    int top_k, int H, int I, int E, int expert_lo, int row_fast,
+    hipStream_t stream) {
+#define CASE(Fmt)                                                            \
+  return moe_routed_prefill_mlp<Fmt>(out, x, topi, topw, w_gate_up, w_down,  \
+                                     gate_up_scale, down_scale, ws, act, y,  \
+                                     T, top_k, H, I, E, expert_lo, row_fast, \
+                                     stream)
+  switch (wformat) {
+    case 0: CASE(PfBf16);
+    case 1: CASE(PfFp8);
+    case 2: CASE(PfMxfp4);
+  }
+#undef CASE
+  return hipErrorInvalidValue;
 }

@@ -1,6 +1,6 @@
 // The weight-only quantized formats (kserve_amd/ops/quant.py) as the kernels
-// see them: what wq_gemm.hip (dense decode GEMM) and moe.hip (routed expert
-// GEMMs) do differently per format. Everything here is exact: E4M3 and
+// see them: what wq_gemm.hip (dense decode GEMM), moe.hip and moe_prefill.hip
+// (routed expert GEMMs) do differently per format. Everything here is exact: E4M3 and
 // E2M1 * 2^e both fit bf16, so the only approximation is the one-time
 // rounding of the weights.
 //
@@ -52,7 +52,12 @@ struct Fp8 {
   // two dwords of fp8 bytes; E4M3 fits bf16's mantissa
   static __device__ __forceinline__ bf16x8_t cvt8(const u32x4_t& w, int kk,
                                                   float) {
-    const unsigned int lo = w[kk * 2], hi = w[kk * 2 + 1];
+    return cvt8(w[kk * 2], w[kk * 2 + 1]);
+  }
+  // the same from the two dwords themselves (moe_prefill.hip reads 8 B of a
+  // W row from LDS per MFMA)
+  static __device__ __forceinline__ bf16x8_t cvt8(const unsigned int lo,
+                                                  const unsigned int hi) {
     const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false);
     const bf16x2_t p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true);
     const bf16x2_t p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false);
@@ -97,7 +102,12 @@ struct Mxfp4 {
   // one dword of fp4 nibbles, times the block scale (a power of two)
   static __device__ __forceinline__ bf16x8_t cvt8(const u32x4_t& w, int kk,
                                                   const float sc) {
-    unsigned int v = w[kk];
+    return cvt8(w[kk], sc);
+  }
+  // the same from the dword itself (moe_prefill.hip reads 4 B of a W row
+  // from LDS per MFMA)
+  static __device__ __forceinline__ bf16x8_t cvt8(unsigned int v,
+                                                  const float sc) {
     if constexpr (SWAP_NIBBLES)
       v = ((v & 0x0f0f0f0fu) << 4) | ((v >> 4) & 0x0f0f0f0fu);
     const bf16x2_t p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, 0);

@@ -25,6 +25,8 @@ grouped kernels (ops.moe_routed_mlp) against the dense-bmm path.
 --moe-prefill is the A/B behind MixtralMoE.ROUTED_PREFILL_MAX_TOKENS (same
 profile, "Prefill"): the same layer at prefill batches, the routed prefill
 kernels (ops.moe_routed_prefill_mlp) against the sparse per-expert loop.
+With --quantization both sides run fp8 / MXFP4 experts and the bf16 prefill
+kernels are timed alongside for orientation.
 """
 
 import argparse
@@ -48,7 +50,9 @@ parser.add_argument("--moe-prefill", action="store_true",
                          "one Mixtral-8x7B layer (profiles/moe_routed.md)")
 parser.add_argument("--quantization", choices=("fp8", "mxfp4"), default=None,
                     help="--moe: the routed layer with experts in this "
-                         "format against the routed bf16 layer")
+                         "format against the routed bf16 layer; "
+                         "--moe-prefill: both sides of the A/B with experts "
+                         "in this format")
 parser.add_argument("--out", default=None,
                     help="--w8/--w4/--moe: also write the table as markdown "
                          "here")
@@ -522,7 +526,14 @@ def bench_moe_prefill():
     2.5 PFLOP/s dense bf16 peak; times are whole calls (align, GEMMs,
     combine, workspace allocations; for the sparse loop its host
     synchronisations too). The check is the test allowance around the sparse
-    result. The last row routes every token to the same two experts."""
+    result. The last row routes every token to the same two experts.
+
+    --quantization q: both sides run the layer's weights quantized per expert
+    to q (the sparse loop then dequantizes every expert it visits into the
+    bf16 scratch, which is what MixtralMoE ran above 384 tokens before the
+    kernels took these formats), and a last column times the bf16 prefill
+    kernels on the same routing. The check column is then only orientation:
+    the sparse side is the looser one (bf16 GEMM outputs and sums)."""
     import statistics
 
     from kserve_amd import ops
@@ -537,6 +548,22 @@ def bench_moe_prefill():
     gen = torch.Generator(device=dev).manual_seed(0)
     moe.w_gate_up.data.normal_(0, H ** -0.5, generator=gen)
     moe.w_down.data.normal_(0, I ** -0.5, generator=gen)
+    q = args.quantization
+    run, scales = moe, {}
+    if q:
+        qcfg = ModelConfig.mixtral_8x7b()
+        qcfg.quantization, qcfg.moe_kernel = q, "routed"
+        with torch.device(dev):
+            run = MixtralMoE(qcfg, dtype=torch.bfloat16)
+        for e in range(E):
+            for name in ("w_gate_up", "w_down"):
+                codes, scale = run.weight_format.shard_to_codes(
+                    getattr(moe, name)[e], None, dev
+                )
+                getattr(run, name).data[e].copy_(codes)
+                getattr(run, name + "_scale").data[e].copy_(scale)
+        scales = dict(gate_up_scale=run.w_gate_up_scale,
+                      down_scale=run.w_down_scale, quantization=q)
 
     def timed(fn, iters):
         t0 = torch.cuda.Event(enable_timing=True)
@@ -551,8 +578,9 @@ def bench_moe_prefill():
     lines = [
         "| T | routing | sparse us | spread | feature-fastest us | spread "
         "| row-fastest us | spread | sparse/best | best TFLOP/s | % of peak "
-        "| max diff / allowance |",
-        "|---|---|---|---|---|---|---|---|---|---|---|---|",
+        "| max diff / allowance |" + (" bf16 kernels us | spread |" if q else ""),
+        "|---|---|---|---|---|---|---|---|---|---|---|---|"
+        + ("---|---|" if q else ""),
     ]
     print(lines[0]); print(lines[1])
     cases = [(T, "uniform") for T in (512, 1024, 2048, 4096, 8192)]
@@ -565,15 +593,23 @@ def bench_moe_prefill():
             topi = topi[:1].expand(T, k).contiguous()
 
         def fs():
-            return moe._forward_sparse(x, topi, topw)
+            return run._forward_sparse(x, topi, topw)
 
         def fr(row_fast):
             ops.MOE_PREFILL_ROW_FAST = row_fast
+            return ops.moe_routed_prefill_mlp(
+                x, topi, topw, run.w_gate_up, run.w_down, 0, **scales
+            )
+
+        def fb():  # orientation: the bf16 kernels, default grid order
+            ops.MOE_PREFILL_ROW_FAST = False
             return ops.moe_routed_prefill_mlp(
                 x, topi, topw, moe.w_gate_up, moe.w_down, 0
             )
 
         variants = (("s", fs), ("f", lambda: fr(False)), ("r", lambda: fr(True)))
+        if q:
+            variants += (("b", fb),)
         iters = max(2, min(20, 16384 // T))  # >= 40 ms per window
         res = {key: [] for key, _ in variants}
         for r in range(rounds + 1):  # round 0 is warm-up
@@ -607,6 +643,8 @@ def bench_moe_prefill():
             f"| {flops / best / 1e6:.0f} | {flops / PEAK_FLOPS * 1e6 / best:.0%} "
             f"| {ratio:.3f} |"
         )
+        if q:
+            line += f" {med['b']:.0f} | {spread['b']:.1%} |"
         print(line, flush=True)
         lines.append(line)
     if args.out:
