@@ -23,7 +23,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 # Sources compiled with packed fp32 instructions (v_pk_*_f32) turned off;
 # new kernels go here.
-NO_PACKED_FP32 = {"moe.hip", "moe_prefill.hip"}
+NO_PACKED_FP32 = {"moe.hip", "moe_prefill.hip", "moe_router.hip"}
 NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 KERNEL_SOURCES = [
@@ -42,6 +42,7 @@ KERNEL_SOURCES = [
     "lora.hip",
     "moe.hip",
     "moe_prefill.hip",
+    "moe_router.hip",
     "gemm8.hip",
     "mfma_probe.hip",
 ]

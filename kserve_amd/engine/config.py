@@ -69,12 +69,24 @@ class ModelConfig:
     moe_kernel: str = field(
         default_factory=lambda: os.environ.get("KS_MOE_KERNEL") or "dense"
     )
+    # the MoE router: "torch" (fp32 linear, softmax, top-k and renorm as
+    # torch ops) or "fused" (one HIP launch, ops.moe_route: selection on the
+    # logits, ties to the lowest expert id, row-invariant bits). Independent
+    # of moe_kernel. The environment variable KS_MOE_ROUTER sets the default.
+    moe_router: str = field(
+        default_factory=lambda: os.environ.get("KS_MOE_ROUTER") or "torch"
+    )
 
     def __post_init__(self):
         if self.moe_kernel not in ("dense", "routed"):
             raise ValueError(
                 f"unknown moe_kernel {self.moe_kernel!r}; "
                 "supported: 'dense', 'routed'"
+            )
+        if self.moe_router not in ("torch", "fused"):
+            raise ValueError(
+                f"unknown moe_router {self.moe_router!r}; "
+                "supported: 'torch', 'fused'"
             )
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_heads

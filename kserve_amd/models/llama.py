@@ -193,6 +193,8 @@ class MixtralMoE(nn.Module):
         self.top_k = config.num_experts_per_tok
         # "routed": decode-sized GPU bf16 batches run ops.moe_routed_mlp
         self.moe_kernel = getattr(config, "moe_kernel", "dense")
+        # "fused": GPU bf16 batches take the router from ops.moe_route
+        self.moe_router = getattr(config, "moe_router", "torch")
         H, inter = config.hidden_size, config.intermediate_size
         # expert parallelism: experts are PARTITIONED across the group
         # (full-width weights per expert) instead of every expert being
@@ -470,12 +472,31 @@ class MixtralMoE(nn.Module):
             )
         )
 
+    def _use_fused_router(self, x: torch.Tensor) -> bool:
+        """moe_router="fused" applies to GPU bf16 batches with a bf16 gate
+        within the kernel's limits, whatever expert path follows."""
+        return (
+            self.moe_router == "fused"
+            and x.is_cuda
+            and x.dtype == torch.bfloat16
+            and self.gate.dtype == torch.bfloat16
+            and ops.moe_route_supported(
+                x.shape[0], self.top_k, x.shape[1], self.num_experts
+            )
+        )
+
     def forward(self, x: torch.Tensor, meta=None) -> torch.Tensor:
         T = x.shape[0]
-        router_logits = torch.nn.functional.linear(x.float(), self.gate.float())
-        probs = torch.softmax(router_logits, dim=-1)
-        topw, topi = probs.topk(self.top_k, dim=-1)
-        topw = topw / topw.sum(dim=-1, keepdim=True)  # mixtral renorm
+        if self._use_fused_router(x):
+            # the gate is replicated under TP and EP: ids are global
+            topi, topw = ops.moe_route(x, self.gate, self.top_k)
+        else:
+            router_logits = torch.nn.functional.linear(
+                x.float(), self.gate.float()
+            )
+            probs = torch.softmax(router_logits, dim=-1)
+            topw, topi = probs.topk(self.top_k, dim=-1)
+            topw = topw / topw.sum(dim=-1, keepdim=True)  # mixtral renorm
         capturing = (
             x.is_cuda and torch.cuda.is_current_stream_capturing()
         )

@@ -872,6 +872,56 @@ def moe_routed_prefill_mlp(
     return out
 
 
+# limits of the fused MoE router (csrc/moe_router.hip; the binding checks them)
+MOE_ROUTE_K_STEP = 32
+MOE_ROUTE_MAX_EXPERTS = 256
+
+
+def moe_route_supported(
+    T: int, top_k: int, hidden: int, num_experts: int
+) -> bool:
+    """Shapes ops.moe_route takes on the GPU (dtype and device aside): any
+    T >= 1, 1 <= num_experts <= 256 (no multiple of anything), 1 <= top_k <=
+    min(8, num_experts) and hidden a multiple of ``MOE_ROUTE_K_STEP``."""
+    return (
+        T >= 1
+        and 1 <= num_experts <= MOE_ROUTE_MAX_EXPERTS
+        and 1 <= top_k <= min(MOE_ROUTED_MAX_TOPK, num_experts)
+        and hidden > 0
+        and hidden % MOE_ROUTE_K_STEP == 0
+    )
+
+
+def moe_route(
+    x: torch.Tensor, gate: torch.Tensor, top_k: int
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Mixture-of-experts router in one launch: x [T, H] bf16, gate [E, H]
+    bf16 -> (topi [T, top_k] int64 global expert ids, topw [T, top_k] f32),
+    the tensors ``moe_routed_mlp`` and ``moe_routed_prefill_mlp`` take.
+
+    logits = x @ gate^T with exact bf16 products summed in f32. topi are the
+    top_k largest LOGITS of the row in descending order, ties to the lowest
+    expert index (not the probabilities: distinct logits may round to one
+    probability). topw_j = exp(l_j - m) / sum over the selected of exp(l - m)
+    with m the row's largest logit, i.e. softmax, top-k and renormalisation;
+    everything after the GEMM is f32. Experts past E (the kernel pads E to a
+    multiple of 16) never win a slot and never enter the sum.
+
+    A row's result depends on that row and the gate alone: it is bit-identical
+    for any T, any position of the row in the batch and from run to run; the
+    order in which a row's K partial sums are added is fixed by H and E. No
+    host synchronisation, and the grid depends on shapes only, so one capture
+    serves any input. Shapes: ``moe_route_supported``. CPU tensors take
+    ``torch_ref.moe_route`` (same formulas and tie rule, f32)."""
+    if not x.is_cuda:
+        return torch_ref.moe_route(x, gate, top_k)
+    T = x.shape[0]
+    topi = torch.empty((T, top_k), dtype=torch.int64, device=x.device)
+    topw = torch.empty((T, top_k), dtype=torch.float32, device=x.device)
+    _native("moe_route").moe_route(topi, topw, x, gate)
+    return topi, topw
+
+
 # -- KV export / import (prefill-decode disaggregation) ----------------------
 
 # device table of the 2L cache base pointers (K0, V0, K1, V1, ...), built the

@@ -100,6 +100,8 @@ hipError_t ks_moe_routed_prefill_mlp(void*, const void*, const void*,
                                      const void*, const void*, int, void*,
                                      void*, void*, int, int, int, int, int,
                                      int, int, hipStream_t);
+hipError_t ks_moe_route(void*, void*, const void*, const void*, int, int, int,
+                        int, hipStream_t);
 hipError_t ks_kv_gather_pages(void*, const void*, const void*, int, int, long,
                               int, int, int, int, hipStream_t);
 hipError_t ks_kv_scatter_pages(const void*, const void*, const void*, int, int,
@@ -999,6 +1001,38 @@ void moe_routed_prefill_mlp_w4(at::Tensor& out, at::Tensor& x,
                   row_fast);
 }
 
+// Fused MoE router (csrc/moe_router.hip): topi [T, k] int64 global expert ids
+// and topw [T, k] f32 <- x [T, H] bf16, gate [E, H] bf16; k = topi.size(1).
+void moe_route(at::Tensor& topi, at::Tensor& topw, at::Tensor& x,
+               at::Tensor& gate) {
+  CHECK_BF16_CONTIG(x);
+  CHECK_BF16_CONTIG(gate);
+  TORCH_CHECK(x.dim() == 2 && gate.dim() == 2 && topi.dim() == 2 &&
+                  gate.size(1) == x.size(1),
+              "moe_route: x [T, H], gate [E, H], topi [T, k]");
+  const int64_t T = x.size(0), H = x.size(1), E = gate.size(0);
+  const int64_t k = topi.size(1);
+  TORCH_CHECK(T >= 1 && T < (int64_t(1) << 31) - 16,
+              "moe_route needs 1 <= T < 2^31 - 16");
+  TORCH_CHECK(E >= 1 && E <= 256, "moe_route needs 1 <= E <= 256 experts");
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= E,
+              "moe_route needs 1 <= top-k <= min(8, E)");
+  TORCH_CHECK(H > 0 && H % 32 == 0, "moe_route needs H % 32 == 0");
+  TORCH_CHECK(topi.scalar_type() == at::kLong && topi.is_cuda() &&
+                  topi.is_contiguous() && topi.size(0) == T,
+              "topi must be a contiguous int64 [T, k] GPU tensor");
+  TORCH_CHECK(topw.scalar_type() == at::kFloat && topw.is_cuda() &&
+                  topw.is_contiguous() && topw.sizes() == topi.sizes(),
+              "topw must be a contiguous f32 [T, k] GPU tensor");
+  TORCH_CHECK(gate.device() == x.device() && topi.device() == x.device() &&
+                  topw.device() == x.device(),
+              "moe_route: all tensors must be on one device");
+  check_hip(ks_moe_route(topi.data_ptr(), topw.data_ptr(), x.data_ptr(),
+                         gate.data_ptr(), (int)T, (int)H, (int)E, (int)k,
+                         current_stream()),
+            "moe_route");
+}
+
 // Shared checks of the KV export/import ops. `caches` is K0, V0, K1, V1, ...
 // and `bases` the device table of their base pointers in the same order
 // (built once by the caller); returns the bytes of one page of one tensor.
@@ -1168,6 +1202,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "routed MoE prefill MLP, fp8 experts with per-row f32 scales");
   m.def("moe_routed_prefill_mlp_w4", &moe_routed_prefill_mlp_w4,
         "routed MoE prefill MLP, MXFP4 experts with E8M0 block scales");
+  m.def("moe_route", &moe_route,
+        "fused MoE router: gate GEMM, top-k on the logits, renormalised "
+        "softmax weights");
   m.def("kv_gather_pages", &kv_gather_pages,
         "gather a request's KV pages of every layer into one buffer");
   m.def("kv_scatter_pages", &kv_scatter_pages,

@@ -443,6 +443,20 @@ def moe_routed_mlp(
     return out.to(x.dtype)
 
 
+def moe_route(x: torch.Tensor, gate: torch.Tensor, top_k: int):
+    """MoE router, f32 reference of ops.moe_route: logits = x @ gate^T
+    accumulated in f32, the top_k largest logits in descending order with
+    ties to the lowest expert index (stable sort), and
+    topw_j = exp(l_j - m) / sum over the selected of exp(l - m), m the row's
+    largest logit. Returns (topi int64 [T, top_k], topw f32 [T, top_k])."""
+    logits = x.float() @ gate.float().t()
+    order = torch.sort(logits, dim=-1, descending=True, stable=True).indices
+    topi = order[:, :top_k].contiguous()
+    sel = logits.gather(1, topi)
+    p = torch.exp(sel - sel[:, :1])
+    return topi, p / p.sum(dim=-1, keepdim=True)
+
+
 def _kv_pages_u8(t: torch.Tensor) -> torch.Tensor:
     """Byte view [num_blocks, Hkv, block_size, D*itemsize] of a cache."""
     return t.view(torch.uint8)

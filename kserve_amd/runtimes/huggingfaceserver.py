@@ -69,6 +69,10 @@ def engine_model_config(args):
     moe_kernel = getattr(args, "moe_kernel", None)
     if moe_kernel is not None:
         model_cfg.moe_kernel = moe_kernel
+    # --moe-router torch|fused: the MoE router as torch ops or one HIP launch
+    moe_router = getattr(args, "moe_router", None)
+    if moe_router is not None:
+        model_cfg.moe_router = moe_router
     return model_cfg
 
 
@@ -198,6 +202,10 @@ def build_parser():
     # HIP kernels (default: KS_MOE_KERNEL, else dense)
     parser.add_argument("--moe-kernel", dest="moe_kernel", default=None,
                         choices=["dense", "routed"])
+    # MoE router: torch ops, or the fused HIP router kernel (default:
+    # KS_MOE_ROUTER, else torch)
+    parser.add_argument("--moe-router", dest="moe_router", default=None,
+                        choices=["torch", "fused"])
     # LoRA adapter serving (reference: --enable-lora --lora-modules name=path)
     parser.add_argument("--speculative-draft-model",
                         dest="speculative_draft_model", default=None,
