@@ -2,25 +2,34 @@
 //
 // MI355X-first design (memory-bound KV read; CDNA guide Appendix B):
 //  - workgroup = (kv_head, seq, split), 4 waves; each wave owns one q head
-//    of the GQA group (two at group 5..8). Every wave reads the group's KV
-//    pages [block=16 tokens][D] itself, straight from global memory with
-//    16 B/lane loads: nothing is staged in LDS, and the page reaches HBM
-//    once only as long as the group's waves read it close enough together
-//    for the 32 KiB L1 to still hold it (4 workgroups x 8 KiB page per CU
-//    fill it exactly).
-//  - online softmax and the PV sum in fp32 registers; the only LDS use is
-//    the per-wave broadcast of a page's 16 probabilities.
+//    of the GQA group (two at group 5..8). In every kernel but the ring
+//    kernel each wave reads the group's KV pages [block=16 tokens][D]
+//    itself, straight from global memory with 16 B/lane loads: nothing is
+//    staged in LDS, and the page reaches HBM once only as long as the
+//    group's waves read it close enough together for the 32 KiB L1 to still
+//    hold it (4 workgroups x 8 KiB page per CU fill it exactly). The ring
+//    kernel of the "v4" slot (paged_attention_v4r_kernel, the default above
+//    128 sequences) fetches each page once per workgroup into a 4-slot LDS
+//    ring with direct global-to-LDS loads, a quarter per wave, and the
+//    waves read their operands from there.
+//  - online softmax and the PV sum in fp32 registers; apart from that ring
+//    the only LDS use is the per-wave broadcast of a page's 16
+//    probabilities.
 //  - split-context (flash-decode style) for small batches: partials
 //    (acc, m, l) to workspace, fused reduction kernel.
 //  - kernels by regime (dispatch at the end of the file): packed-dot "d2"
 //    up to 128 sequences, the wide-V "v4" slot above that
-//    (paged_attention_v4p_kernel, or paged_attention_kernel's V4 path with
-//    KS_ATTN_V4PIPE=0), the generic path for D=64 and groups 5..8.
+//    (paged_attention_v4r_kernel; with KS_ATTN_V4RING=0
+//    paged_attention_v4p_kernel, and with KS_ATTN_V4PIPE=0 as well
+//    paged_attention_kernel's V4 path; all three give the same bits), the
+//    generic path for D=64 and groups 5..8.
 //
 // Replaces the vLLM paged-attention path the reference delegates to
 // (SURVEY.md §2.7 row 1).
+#include "attn_ring_layout.h"
 #include "common.h"
 #include "mfma_layouts.h"
+#include "skinny_shared.h"
 
 #define NEG_INF (-1e30f)
 
@@ -30,6 +39,10 @@ constexpr int PAGE = 16;      // tokens per KV page
 constexpr int NWAVES = 4;     // waves per workgroup
 // which page loop the wide-V "v4" slot launches when KS_ATTN_V4PIPE is unset
 constexpr bool V4PIPE_DEFAULT = true;
+// whether that slot launches the LDS-ring kernel when KS_ATTN_V4RING is
+// unset, and the ring's page slots (profiles/attn_decode_bench.md)
+constexpr bool V4RING_DEFAULT = true;
+constexpr int V4RING_SLOTS = 4;
 
 // D: head dim (64 or 128). ACC = D/64 output dims per lane.
 // HPW: q heads per wave (GQA group = NWAVES*HPW covered per workgroup).
@@ -1276,6 +1289,281 @@ __global__ __launch_bounds__(256) void paged_attention_v4p_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// LDS-ring wide-V kernel (the "v4" slot; KS_ATTN_V4RING). Same grid, lane
+// layouts, partial format and per-page arithmetic as
+// paged_attention_v4p_kernel: compute_page below is that kernel's, line for
+// line, so the outputs are the same bits. What differs is how K and V reach
+// it. In v4p every one of the four waves loads the whole 8 KiB page (4 K + 4
+// V dwordx4 per lane) and the L1 serves three of the four; here a page
+// crosses the L1 once per workgroup:
+//  - ring of R page slots in LDS (attn_ring_layout.h), page p in slot p % R.
+//    Each wave fetches its quarter of a page with one K and one V
+//    global_load_lds_dwordx4 per lane: the bytes go from memory into LDS
+//    without passing through VGPRs. Such a load puts lane i's 16 bytes at
+//    base + 16 * i, so the K chunk swizzle that keeps the ds_read_b128 of
+//    the QK layout apart is applied to the source address.
+//  - per page pair t a wave: waits (s_waitcnt vmcnt) until its own quarters
+//    of pages 2t, 2t+1 have landed, meets the other waves at one s_barrier
+//    ((npages + 1) / 2 in all, as in v4p), issues the 4 + 4 ds_read_b128 of
+//    pages 2t and 2t + 1, then its quarters of pages 2t + R - 2 and
+//    2t + R - 1 into the slots of pages 2t - 2 and 2t - 1, which every wave
+//    has finished reading once it is at this barrier, and computes pages 2t
+//    and 2t + 1 under those fetches. With one barrier per pair the pair in
+//    compute and the pair just read still own their slots, so R slots put
+//    R - 2 pages ahead: R = 4 ships, two pages (16 KiB) in flight per
+//    workgroup, and its wait is a vmcnt(0) because nothing younger is in
+//    flight at that point. A deeper ring (R = 6: vmcnt(4)) compiles, but the
+//    compiler puts a wait for every outstanding LDS load in front of any
+//    ds_read of the ring, so it would need operand reads the compiler does
+//    not track; R = 2 and 3 have no free slot to fetch into at the barrier.
+//  - waves without a q head (group < 4) fetch their quarters and meet every
+//    barrier; they skip the reads and the arithmetic.
+//  - block ids as in v4p: 64 table entries per vector load, this chunk's and
+//    the next one's held in two VGPRs, v_readlane per page. Every page index,
+//    prefetched ones included, is clamped to the range's last page first, so
+//    no table entry past blk_hi - 1 is read; a clamped fetch re-reads the
+//    last page into a free slot and nobody reads it.
+// ---------------------------------------------------------------------------
+template <int R>
+__global__ __launch_bounds__(256) void paged_attention_v4r_kernel(
+    short* __restrict__ out, const short* __restrict__ q,
+    const short* __restrict__ k_cache, const short* __restrict__ v_cache,
+    const int* __restrict__ block_tables, const int* __restrict__ context_lens,
+    const float scale, const int num_kv_heads, const int group,
+    const int max_blocks, const long q_row_stride, const int n_splits,
+    float* __restrict__ part_out, float* __restrict__ part_ml,
+    const int window) {
+  static_assert(R >= 4 && R % 2 == 0, "pairs: an even ring of at least 4");
+  constexpr int D = 128;
+  constexpr int QFRAG = D / 4;
+  constexpr int AHEAD = R - 2;  // pages in flight past the pair in compute
+  const int kv_head = blockIdx.x;
+  const int seq = blockIdx.y;
+  const int split = blockIdx.z;
+  const int ctx = context_lens[seq];
+  if (ctx <= 0) return;
+  const int num_heads = num_kv_heads * group;
+  const int lane = threadIdx.x & 63;
+  // wave-uniform by construction: LDS-load destinations and the branches
+  // around compute must be scalar
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tok = lane >> 2;   // QK: token within the page
+  const int part = lane & 3;   // QK: quarter of D
+  const int vtok = lane >> 4;  // PV: tokens vtok, 4+vtok, 8+vtok, 12+vtok
+  const int vdim = (lane & 15) * 8;
+  __shared__ __attribute__((aligned(16))) float p_bc[NWAVES][PAGE];
+  __shared__ __attribute__((aligned(16))) unsigned char
+      ring[R * ring_layout::SLOT_BYTES];
+
+  const int nblocks = (ctx + PAGE - 1) / PAGE;
+  // sliding window: only pages holding the last `window` tokens are read
+  const int wstart = (window > 0 && ctx > window) ? ctx - window : 0;
+  const int first_blk = wstart / PAGE;
+  const int blocks_per_split =
+      (nblocks - first_blk + n_splits - 1) / n_splits;
+  const int blk_lo = first_blk + split * blocks_per_split;
+  const int blk_hi = min(nblocks, blk_lo + blocks_per_split);
+  if (blk_lo >= blk_hi) {
+    // record empty partial so the reducer can skip it
+    if (n_splits > 1 && threadIdx.x < (unsigned)group) {
+      const int h = kv_head * group + threadIdx.x;
+      float* ml = part_ml + (((long)seq * num_heads + h) * n_splits + split) * 2;
+      ml[0] = NEG_INF;
+      ml[1] = 0.f;
+    }
+    return;
+  }
+  const int npages = blk_hi - blk_lo;
+  const bool active = wave < group;  // this wave has a q head
+  const int head = kv_head * group + wave;
+
+  float q_frag[QFRAG];
+  if (active) {
+    const short* qp =
+        q + (long)seq * q_row_stride + (long)head * D + part * QFRAG;
+#pragma unroll
+    for (int j = 0; j < QFRAG; ++j) q_frag[j] = bf16_bits_to_float(qp[j]);
+  }
+
+  const int* bt_row = block_tables + (long)seq * max_blocks + blk_lo;
+  // lane j <- table entry of page c0 + j, never past the range's last
+  auto load_ids = [&](int c0) {
+    return bt_row[min(c0 + lane, npages - 1)];
+  };
+  const long head_off = (long)kv_head * PAGE * D;
+  const long blk_stride = (long)num_kv_heads * PAGE * D;
+  // this lane's 16 bytes of the wave's quarter, as element offsets
+  const int k_src = ring_layout::k_src_byte(wave, lane) / 2;
+  const int v_src = ring_layout::v_src_byte(wave, lane) / 2;
+  unsigned char* const my_quarter = ring + wave * (64 * ring_layout::CHUNK);
+  auto fetch_page = [&](int block_id, int slot) {
+    const long pbase = (long)block_id * blk_stride + head_off;
+    unsigned char* dst = my_quarter + slot * ring_layout::SLOT_BYTES;
+    __builtin_amdgcn_global_load_lds(
+        reinterpret_cast<const unsigned int*>(k_cache + pbase + k_src),
+        reinterpret_cast<unsigned int*>(dst), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(
+        reinterpret_cast<const unsigned int*>(v_cache + pbase + v_src),
+        reinterpret_cast<unsigned int*>(dst + ring_layout::HALF_BYTES), 16, 0,
+        0);
+  };
+  // this lane's operand addresses inside a slot
+  int k_rd[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) k_rd[c] = ring_layout::k_read_byte(lane, c);
+  const int v_rd = ring_layout::HALF_BYTES + ring_layout::v_read_byte(lane, 0);
+  constexpr int V_RD_STEP =
+      ring_layout::v_read_byte(0, 1) - ring_layout::v_read_byte(0, 0);
+  auto read_page = [&](int slot, short8_t* kreg, short8_t* vreg) {
+    const unsigned char* s = ring + slot * ring_layout::SLOT_BYTES;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      kreg[c] = *reinterpret_cast<const short8_t*>(s + k_rd[c]);
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4)
+      vreg[q4] =
+          *reinterpret_cast<const short8_t*>(s + v_rd + q4 * V_RD_STEP);
+  };
+
+  float m = NEG_INF;
+  float l = 0.f;
+  float acc8[8];
+#pragma unroll
+  for (int a = 0; a < 8; ++a) acc8[a] = 0.f;
+  float* pw = &p_bc[wave][(tok & 3) * 4 + (tok >> 2)];
+  const float4_t* pr = reinterpret_cast<const float4_t*>(&p_bc[wave][vtok * 4]);
+
+  auto compute_page = [&](int bi, const short8_t* kreg,
+                          const short8_t* vreg) {
+    // paged_attention_v4p_kernel's compute_page, unchanged: every rounding
+    // is pinned (that kernel's header: "same bits"), so nothing here may be
+    // reassociated.
+#pragma clang fp reassociate(off)
+    float lo = 0.f, hi = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int r = i & 3, g = i >> 2;
+      const int c = r == 0 ? 1 : (r == 1 ? 0 : r);               // 1,0,2,3
+      const int w = g == 0 ? 2 : (g == 1 ? 0 : (g == 2 ? 3 : 1));  // 2,0,3,1
+      const float kl = bf16_bits_to_float(kreg[c][2 * w]);
+      const float kh = bf16_bits_to_float(kreg[c][2 * w + 1]);
+      const float ql = q_frag[c * 8 + 2 * w], qh = q_frag[c * 8 + 2 * w + 1];
+      lo = i == 0 ? ql * kl : __builtin_fmaf(ql, kl, lo);
+      hi = i == 0 ? qh * kh : __builtin_fmaf(qh, kh, hi);
+    }
+    float s = lo + hi;
+    s += dpp_mov<DPP_QUAD_XOR2>(s);
+    s += dpp_mov<DPP_QUAD_XOR1>(s);
+    const int gtok = bi * PAGE + tok;
+    s = (gtok < ctx && gtok >= wstart) ? s * scale : NEG_INF;
+    float tmax = fmaxf(s, dpp_mov<DPP_ROW_ROR4>(s));
+    tmax = fmaxf(tmax, dpp_mov<DPP_ROW_ROR8>(tmax));
+    tmax = rows_max(tmax);
+    const float m_new = fmaxf(m, tmax);
+    const float rescale = __expf(m - m_new);
+    const float p = (s > NEG_INF) ? __expf(s - m_new) : 0.f;
+    float psum = p + dpp_mov<DPP_ROW_HALF_MIRROR>(p);
+    psum += dpp_mov<DPP_ROW_MIRROR>(psum);
+    psum = rows_sum(psum);
+    l = __builtin_fmaf(l, rescale, psum);
+    m = m_new;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    if (part == 0) *pw = p;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    const float4_t pt4 = *pr;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int a = 0; a < 8; ++a) acc8[a] *= rescale;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const float pt = pt4[q4];
+#pragma unroll
+      for (int a = 0; a < 8; ++a)
+        acc8[a] = __builtin_fmaf(pt, bf16_bits_to_float(vreg[q4][a]), acc8[a]);
+    }
+  };
+
+  // ids: entries of the 64-page chunk that holds the pair in compute;
+  // ids_next: the chunk after it (a fetch runs at most AHEAD + 1 < 64 pages
+  // ahead)
+  int ids = load_ids(0);
+  int ids_next = load_ids(64);
+  int c0 = 0;
+  auto page_id = [&](int p) {
+    p = min(p, npages - 1);
+    const int a = __builtin_amdgcn_readlane(ids, p & 63);
+    const int b = __builtin_amdgcn_readlane(ids_next, p & 63);
+    return p - c0 < 64 ? a : b;
+  };
+  for (int p = 0; p < AHEAD; ++p) fetch_page(page_id(p), p % R);
+
+  // a wave has 4 loads per pair in the queue; all pairs younger than the
+  // one about to be computed may stay in flight
+  constexpr int WAIT_PAIR = waitcnt_vmcnt(4 * (AHEAD / 2 - 1));
+  short8_t kA[4], vA[4], kB[4], vB[4];
+  for (int p = 0; p < npages; p += 2) {
+    const bool next_chunk = p - c0 == 64;
+    if (next_chunk) {
+      c0 = p;
+      ids = ids_next;
+    }
+    __builtin_amdgcn_s_waitcnt(WAIT_PAIR);  // own quarters of p, p + 1 landed
+    __builtin_amdgcn_sched_barrier(0);
+    // everyone's quarters of p, p + 1 are in LDS, and everyone is done with
+    // pages p - 2, p - 1
+    __builtin_amdgcn_s_barrier();
+    // The operand reads are issued ahead of the fetches: the compiler puts
+    // a wait for every LDS load still in flight in front of a ds_read of
+    // the ring, and here that is the wait above, not one for the pages
+    // fetched below.
+    if (active) {
+      read_page(p % R, kA, vA);
+      read_page((p + 1) % R, kB, vB);
+    }
+    fetch_page(page_id(p + AHEAD), (p + AHEAD) % R);
+    fetch_page(page_id(p + AHEAD + 1), (p + AHEAD + 1) % R);
+    // the table load goes behind the fetches, so the wait above never
+    // waits for it; no fetch reaches into the chunk after ids for 56 pages
+    if (next_chunk) ids_next = load_ids(c0 + 64);
+    if (active) {
+      compute_page(blk_lo + p, kA, vA);
+      if (p + 1 < npages) compute_page(blk_lo + p + 1, kB, vB);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  // nothing of this workgroup may still be writing LDS when it ends
+  __builtin_amdgcn_s_waitcnt(waitcnt_vmcnt(0));
+  if (!active) return;
+
+  // cross token-slice reduction (deferred from the per-page PV): lanes
+  // sharing lane%16 hold 4-token partials of the same 8 dims
+#pragma unroll
+  for (int a = 0; a < 8; ++a) acc8[a] = rows_sum(acc8[a]);
+  if (n_splits == 1) {
+    const float inv_l = (l > 0.f) ? 1.f / l : 0.f;
+    if (lane < 16) {
+      short* op = out + ((long)seq * num_heads + head) * D + vdim;
+#pragma unroll
+      for (int a = 0; a < 8; ++a) op[a] = float_to_bf16_bits(acc8[a] * inv_l);
+    }
+  } else {
+    if (lane < 16) {
+      float* po = part_out +
+                  (((long)seq * num_heads + head) * n_splits + split) * D +
+                  vdim;
+#pragma unroll
+      for (int a = 0; a < 8; ++a) po[a] = acc8[a];
+    }
+    if (lane == 0) {
+      float* ml =
+          part_ml + (((long)seq * num_heads + head) * n_splits + split) * 2;
+      ml[0] = m;
+      ml[1] = l;
+    }
+  }
+}
+
 // Combine split-context partials: one wave per (seq, head); lane owns D/64
 // dims across all splits.
 template <int D>
@@ -1514,8 +1802,22 @@ extern "C" hipError_t ks_paged_attention_decode(
     const char* e = getenv("KS_ATTN_V4PIPE");
     return e ? e[0] == '1' : V4PIPE_DEFAULT;
   }();
+  // KS_ATTN_V4RING=1 the LDS-ring kernel (each page fetched once per
+  // workgroup; same bits as the pipelined kernel), =0 off; unset takes
+  // V4RING_DEFAULT
+  static const bool v4_ring = [] {
+    const char* e = getenv("KS_ATTN_V4RING");
+    return e ? e[0] == '1' : V4RING_DEFAULT;
+  }();
   if (use_v4 && hpw == 1 && head_dim == 128) {
-    if (v4_pipe && !v4_d2) {
+    if (v4_ring && !v4_d2) {
+      hipLaunchKernelGGL(
+          paged_attention_v4r_kernel<V4RING_SLOTS>, grid, block, 0, stream,
+          (short*)out, (const short*)q, (const short*)k_cache,
+          (const short*)v_cache, (const int*)block_tables,
+          (const int*)context_lens, scale, num_kv_heads, group, max_blocks,
+          q_row_stride, n_splits, (float*)part_out, (float*)part_ml, window);
+    } else if (v4_pipe && !v4_d2) {
       hipLaunchKernelGGL(
           paged_attention_v4p_kernel, grid, block, 0, stream, (short*)out,
           (const short*)q, (const short*)k_cache, (const short*)v_cache,

@@ -300,6 +300,39 @@ void paged_attention_decode(at::Tensor& out, at::Tensor& q,
             "paged_attention_decode");
 }
 
+// bf16 decode attention at a given split count that hands the split partials
+// back: (part_out [S, H, n_splits, D], part_ml [S, H, n_splits, 2]), fp32.
+// For tests that compare kernels partial by partial.
+std::tuple<at::Tensor, at::Tensor> paged_attention_decode_split(
+    at::Tensor& out, at::Tensor& q, at::Tensor& k_cache, at::Tensor& v_cache,
+    at::Tensor& block_tables, at::Tensor& context_lens, double scale,
+    int64_t window, int64_t n_splits) {
+  CHECK_BF16_CONTIG(out);
+  CHECK_BF16_ROWS(q);
+  CHECK_KV_CACHE(k_cache);
+  CHECK_KV_CACHE(v_cache);
+  TORCH_CHECK(k_cache.scalar_type() == at::kBFloat16, "bf16 cache only");
+  TORCH_CHECK(block_tables.scalar_type() == at::kInt, "block_tables int32");
+  TORCH_CHECK(context_lens.scalar_type() == at::kInt, "context_lens int32");
+  TORCH_CHECK(block_tables.is_contiguous(), "block_tables must be contiguous");
+  TORCH_CHECK(context_lens.is_contiguous(), "context_lens must be contiguous");
+  TORCH_CHECK(n_splits >= 2 && n_splits <= 16, "n_splits in 2..16");
+  const int S = q.size(0), H = q.size(1), D = q.size(2);
+  auto opts = at::TensorOptions().dtype(at::kFloat).device(q.device());
+  at::Tensor part_out = at::zeros({S, H, n_splits, D}, opts);
+  at::Tensor part_ml = at::zeros({S, H, n_splits, 2}, opts);
+  check_hip(ks_paged_attention_decode(
+                out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
+                v_cache.data_ptr(), block_tables.data_ptr(),
+                context_lens.data_ptr(), (float)scale, S, H,
+                (int)k_cache.size(1), D, (int)block_tables.size(1),
+                (int)k_cache.size(2), (long)q.stride(0), (int)n_splits,
+                part_out.data_ptr(), part_ml.data_ptr(), (int)window,
+                current_stream()),
+            "paged_attention_decode_split");
+  return {part_out, part_ml};
+}
+
 void flash_prefill_varlen(at::Tensor& out, at::Tensor& q, at::Tensor& k,
                           at::Tensor& v, at::Tensor& cu_seqlens,
                           int64_t max_seqlen, double scale,
@@ -1147,6 +1180,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reshape_and_cache", &reshape_and_cache, "KV page scatter");
   m.def("paged_attention_decode", &paged_attention_decode,
         "paged decode attention (GQA, split-context)");
+  m.def("paged_attention_decode_split", &paged_attention_decode_split,
+        "bf16 paged decode attention at a given split count; returns the "
+        "fp32 split partials");
   m.def("flash_prefill_varlen", &flash_prefill_varlen,
         "MFMA flash attention (varlen GQA, causal or bidirectional)",
         pybind11::arg("out"), pybind11::arg("q"), pybind11::arg("k"),
