@@ -23,7 +23,9 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 # Sources compiled with packed fp32 instructions (v_pk_*_f32) turned off;
 # new kernels go here.
-NO_PACKED_FP32 = {"moe.hip", "moe_prefill.hip", "moe_router.hip"}
+NO_PACKED_FP32 = {
+    "moe.hip", "moe_prefill.hip", "moe_router.hip", "wq_tile_gemm.hip",
+}
 NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 KERNEL_SOURCES = [
@@ -39,6 +41,7 @@ KERNEL_SOURCES = [
     "logit_process.hip",
     "skinny_gemm.hip",
     "wq_gemm.hip",
+    "wq_tile_gemm.hip",
     "lora.hip",
     "moe.hip",
     "moe_prefill.hip",

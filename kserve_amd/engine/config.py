@@ -76,8 +76,21 @@ class ModelConfig:
     moe_router: str = field(
         default_factory=lambda: os.environ.get("KS_MOE_ROUTER") or "torch"
     )
+    # how quantized projections run batches above the skinny GEMM's range:
+    # "dequant" (dequantize into the scratch, then hipBLASLt) or "tile" (the
+    # fused-dequant MFMA tile GEMM, ops.linear_w8 / linear_w4 with tile=True,
+    # up to ops.WQ_TILE_MAX_TOKENS). The environment variable KS_QUANT_GEMM
+    # sets the default.
+    quant_gemm: str = field(
+        default_factory=lambda: os.environ.get("KS_QUANT_GEMM") or "dequant"
+    )
 
     def __post_init__(self):
+        if self.quant_gemm not in ("dequant", "tile"):
+            raise ValueError(
+                f"unknown quant_gemm {self.quant_gemm!r}; "
+                "supported: 'dequant', 'tile'"
+            )
         if self.moe_kernel not in ("dense", "routed"):
             raise ValueError(
                 f"unknown moe_kernel {self.moe_kernel!r}; "

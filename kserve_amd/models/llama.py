@@ -29,6 +29,7 @@ from kserve_amd.parallel.layers import (
     QKVParallelLinear,
     RowParallelLinear,
     VocabParallelEmbedding,
+    _QuantLinearBase,
 )
 
 
@@ -649,6 +650,11 @@ class LlamaForCausalLM(nn.Module):
             persistent=False,
         )
         self.eps = config.rms_norm_eps
+        # how the quantized projections run batches above the skinny GEMM's
+        # range (ModelConfig.quant_gemm; unquantized layers ignore it)
+        for mod in self.modules():
+            if isinstance(mod, _QuantLinearBase):
+                mod.quant_gemm = getattr(config, "quant_gemm", "dequant")
         self.to(device)
 
     # -- init ---------------------------------------------------------------

@@ -262,6 +262,14 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 # (A/B table: profiles/w8_gemm.md, tools/gemm_bench.py --w8).
 W8_MAX_TOKENS = 128
 
+# Largest token batch that linear_w8 / linear_w4 with tile=True send to the
+# fused-dequant tile GEMM (csrc/wq_tile_gemm.hip); above it the dequant path
+# runs. Per format the largest measured N (129, 256, 512, 1024, 1536, 2048,
+# 4096) up to which the kernel was no slower than dequant + hipBLASLt on all
+# four Llama-3-8B projection shapes; at 1024 qkv and o lose (A/B tables:
+# profiles/wq_tile_gemm.md, tools/gemm_bench.py --wq-tile).
+WQ_TILE_MAX_TOKENS = {"fp8": 512, "mxfp4": 512}
+
 # One bf16 dequant scratch per device, shared by every quantized layer
 # (same-stream ordering: a GEMM has consumed it before the next dequant
 # overwrites it). It holds HALF of the largest quantized weight: the
@@ -320,31 +328,51 @@ def _linear_wq(
     gemm: str,  # binding names
     dequant: str,
     reference,  # CPU path
+    tile_gemm: Optional[str] = None,  # tile binding and its token limit
+    tile_max_tokens: int = 0,
 ) -> torch.Tensor:
     """What linear_w8 and linear_w4 share. GPU: decode-sized batches run the
-    format's MFMA skinny GEMM (weights cross HBM once, as codes); everything
-    else (prefill, large batches, odd shapes) dequantizes into the shared
-    scratch, in row chunks, and runs hipBLASLt."""
+    format's MFMA skinny GEMM (weights cross HBM once, as codes); with
+    ``tile_gemm``, batches above that and up to ``tile_max_tokens`` run the
+    fused-dequant MFMA tile GEMM (csrc/wq_tile_gemm.hip, bias fused);
+    everything else (prefill, large batches, odd shapes) dequantizes into the
+    shared scratch, in row chunks, and runs hipBLASLt."""
     if not x.is_cuda:
         return reference(x, qweight, scale, bias)
     C = _native(name)
     import torch.nn.functional as F
 
     M = qweight.shape[0]
-    if (
+    shape_ok = (
         x.dim() == 2
-        and 0 < x.shape[0] <= max_tokens
+        and x.shape[0] > 0
         and M % 64 == 0
         and K % k_multiple == 0
         and x.dtype == torch.bfloat16
         and x.stride(1) == 1
         and x.stride(0) % 8 == 0
         and x.data_ptr() % 16 == 0
-    ):
+    )
+    if shape_ok and x.shape[0] <= max_tokens:
         out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
         getattr(C, gemm)(out, x, qweight, scale)
         if bias is not None:
             out += bias
+        return out
+    if (
+        tile_gemm is not None
+        and shape_ok
+        and x.shape[0] <= tile_max_tokens
+        and qweight.data_ptr() % 16 == 0
+        and scale.data_ptr() % 16 == 0
+        and (
+            bias is None
+            or (bias.dtype == torch.bfloat16 and bias.data_ptr() % 8 == 0
+                and bias.is_contiguous())
+        )
+    ):
+        out = torch.empty((x.shape[0], M), dtype=x.dtype, device=x.device)
+        getattr(C, tile_gemm)(out, x, qweight, scale, bias, 0)
         return out
     if x.dtype != torch.bfloat16:
         raise TypeError(f"{name} on GPU needs bf16 activations, got {x.dtype}")
@@ -366,16 +394,23 @@ def linear_w8(
     qweight: torch.Tensor,
     scale: torch.Tensor,
     bias: Optional[torch.Tensor] = None,
+    *,
+    tile: bool = False,
 ) -> torch.Tensor:
     """Weight-only fp8 linear: (x @ qweight^T) * scale (+ bias).
 
     qweight [M, K] float8_e4m3fn, scale [M] f32 (kserve_amd.ops.quant).
+    ``tile``: batches above W8_MAX_TOKENS and up to
+    WQ_TILE_MAX_TOKENS["fp8"] run the fused-dequant tile GEMM instead of
+    dequant + hipBLASLt (GPU only).
     """
     return _linear_wq(
         "linear_w8", x, qweight, scale, bias,
         K=qweight.shape[1], k_multiple=64, max_tokens=W8_MAX_TOKENS,
         gemm="skinny_gemm_w8", dequant="dequant_fp8_rows",
         reference=torch_ref.linear_w8,
+        tile_gemm="wq_tile_gemm_w8" if tile else None,
+        tile_max_tokens=WQ_TILE_MAX_TOKENS["fp8"],
     )
 
 
@@ -394,18 +429,23 @@ def linear_w4(
     qweight: torch.Tensor,
     weight_scale: torch.Tensor,
     bias: Optional[torch.Tensor] = None,
+    *,
+    tile: bool = False,
 ) -> torch.Tensor:
     """Weight-only MXFP4 linear: x @ dequant(qweight, weight_scale)^T (+ bias).
 
     qweight uint8 [M, K/2], weight_scale uint8 [M, K/32]
     (kserve_amd.ops.quant); the weights cross HBM as 4.25 bits each. The
-    dequant scratch is the one linear_w8 uses.
+    dequant scratch is the one linear_w8 uses. ``tile`` as in linear_w8,
+    up to WQ_TILE_MAX_TOKENS["mxfp4"].
     """
     return _linear_wq(
         "linear_w4", x, qweight, weight_scale, bias,
         K=qweight.shape[1] * 2, k_multiple=128, max_tokens=W4_MAX_TOKENS,
         gemm="skinny_gemm_w4", dequant="dequant_mxfp4_rows",
         reference=torch_ref.linear_w4,
+        tile_gemm="wq_tile_gemm_w4" if tile else None,
+        tile_max_tokens=WQ_TILE_MAX_TOKENS["mxfp4"],
     )
 
 

@@ -75,6 +75,10 @@ hipError_t ks_dequant_mxfp4_rows(void*, const void*, const void*, long, int,
                                  hipStream_t);
 hipError_t ks_dequant_fp8_rows(void*, const void*, const void*, long, int,
                                hipStream_t);
+int ks_wq_tile_nsplit(int, int);
+hipError_t ks_wq_tile_gemm(void*, void*, const void*, const void*,
+                           const void*, const void*, int, int, int, int, long,
+                           int, int, hipStream_t);
 hipError_t ks_lora_shrink(void*, const void*, const void*, const void*,
                           const void*, int, int, int, int, long, hipStream_t);
 hipError_t ks_lora_expand_add(void*, const void*, const void*, const void*,
@@ -677,6 +681,78 @@ void dequant_mxfp4_rows(at::Tensor& out, at::Tensor& qweight,
             "dequant_mxfp4_rows");
 }
 
+// The fused-dequant tile GEMMs (wq_tile_gemm.hip), after their own weight
+// check: wformat 1 = fp8, 2 = MXFP4, wK the K that qweight holds, BK the
+// format's K multiple. n_splits 0 = the (M, K) policy, else forced.
+void wq_tile_gemm(const char* op, int wformat, int64_t wK, int BK,
+                  at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
+                  at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                  int64_t n_splits, bool plain_order) {
+  CHECK_BF16_CONTIG(out);
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.is_cuda() &&
+                  x.dim() == 2 && x.stride(1) == 1 &&
+                  x.stride(0) % 8 == 0 && x.stride(0) >= x.size(1) &&
+                  ((uintptr_t)x.data_ptr() & 15) == 0,
+              "x must be bf16 row-dense, 16-byte aligned, row stride % 8 == 0");
+  int N = x.size(0);
+  int K = x.size(1);
+  int M = qweight.size(0);
+  TORCH_CHECK(wK == K && out.dim() == 2 && out.size(0) == N &&
+                  out.size(1) == M,
+              "shape mismatch");
+  TORCH_CHECK(N >= 1 && M % 64 == 0 && K >= BK && K % BK == 0, op,
+              " needs N >= 1, M % 64 == 0, K % ", BK, " == 0");
+  TORCH_CHECK(((uintptr_t)qweight.data_ptr() & 15) == 0 &&
+                  ((uintptr_t)scale.data_ptr() & 15) == 0,
+              "qweight and scale must be 16-byte aligned");
+  const void* bias_ptr = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_cuda() &&
+                    bias->is_contiguous() && bias->numel() == M &&
+                    ((uintptr_t)bias->data_ptr() & 7) == 0,
+                "bias must be bf16 [out_features] on GPU, 8-byte aligned");
+    bias_ptr = bias->data_ptr();
+  }
+  int S = n_splits == 0 ? ks_wq_tile_nsplit(M, K) : (int)n_splits;
+  TORCH_CHECK((S == 1 || S == 2 || S == 4 || S == 8) && (K / 64) % S == 0, op,
+              ": n_splits must be 0, 1, 2, 4 or 8 and divide K / 64");
+  at::Tensor part;
+  if (S > 1)
+    part = at::empty({(long)S, (long)N, (long)M},
+                     x.options().dtype(at::kFloat));
+  check_hip(ks_wq_tile_gemm(out.data_ptr(),
+                            part.defined() ? part.data_ptr() : nullptr,
+                            x.data_ptr(), qweight.data_ptr(),
+                            scale.data_ptr(), bias_ptr, wformat, M, K, N,
+                            (long)x.stride(0), S, plain_order ? 1 : 0,
+                            current_stream()),
+            op);
+}
+
+void wq_tile_gemm_w8(at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
+                     at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                     int64_t n_splits, bool plain_order) {
+  // out [N, M] bf16 = (x [N, K] bf16 @ qweight [M, K]^T e4m3) * scale [M]
+  //                   + bias [M]
+  CHECK_FP8_WEIGHT(qweight, scale);
+  wq_tile_gemm("wq_tile_gemm_w8", 1, qweight.size(1), 64, out, x, qweight,
+               scale, bias, n_splits, plain_order);
+}
+
+void wq_tile_gemm_w4(at::Tensor& out, at::Tensor& x, at::Tensor& qweight,
+                     at::Tensor& scale, const c10::optional<at::Tensor>& bias,
+                     int64_t n_splits, bool plain_order) {
+  // out [N, M] bf16 = x [N, K] bf16 @ dequant(qweight [M, K/2], scale)^T
+  //                   + bias [M]
+  CHECK_MXFP4_WEIGHT(qweight, scale);
+  wq_tile_gemm("wq_tile_gemm_w4", 2, qweight.size(1) * 2, 128, out, x,
+               qweight, scale, bias, n_splits, plain_order);
+}
+
+int64_t wq_tile_nsplit(int64_t M, int64_t K) {
+  return ks_wq_tile_nsplit((int)M, (int)K);
+}
+
 // [T, cols] bf16 rows of a possibly wider buffer: unit inner stride, every
 // row start 16-byte aligned (the LoRA kernels use 16 B / 8 B vectors)
 #define CHECK_LORA_ROWS(t)                                                 \
@@ -1214,6 +1290,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "decode GEMM, MXFP4 weights x bf16 activations (N<=128)");
   m.def("dequant_mxfp4_rows", &dequant_mxfp4_rows,
         "MXFP4 rows (e2m1 codes, e8m0 block scales) -> bf16");
+  m.def("wq_tile_gemm_w8", &wq_tile_gemm_w8,
+        "tile GEMM, fp8 e4m3 weights x bf16 activations, any N (fused "
+        "dequant, bias and split-K)",
+        pybind11::arg("out"), pybind11::arg("x"), pybind11::arg("qweight"),
+        pybind11::arg("scale"), pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("n_splits") = 0, pybind11::arg("plain_order") = false);
+  m.def("wq_tile_gemm_w4", &wq_tile_gemm_w4,
+        "tile GEMM, MXFP4 weights x bf16 activations, any N (fused dequant, "
+        "bias and split-K)",
+        pybind11::arg("out"), pybind11::arg("x"), pybind11::arg("qweight"),
+        pybind11::arg("scale"), pybind11::arg("bias") = pybind11::none(),
+        pybind11::arg("n_splits") = 0, pybind11::arg("plain_order") = false);
+  m.def("wq_tile_nsplit", &wq_tile_nsplit,
+        "K splits the tile GEMMs choose for an [M, K] weight");
   m.def("lora_shrink", &lora_shrink,
         "batched multi-LoRA shrink: tmp = x . A[slot]^T per row (f32 out)");
   m.def("lora_expand_add", &lora_expand_add,

@@ -35,7 +35,13 @@ class _QuantLinearBase(nn.Module):
     quantization="mxfp4": ``qweight`` (uint8 [out_local, in_local/2], two
     E2M1 codes per byte) + ``weight_scale`` (uint8 [out_local,
     in_local/32], E8M0), again instead of ``weight``.
+
+    ``quant_gemm`` (ModelConfig.quant_gemm; the model sets it after building
+    its layers): "dequant", or "tile" for the fused-dequant tile GEMM on
+    batches above the skinny GEMM's range.
     """
+
+    quant_gemm = "dequant"
 
     def _alloc_weight(
         self, out_local: int, in_local: int, dtype: torch.dtype,
@@ -113,7 +119,8 @@ class _QuantLinearBase(nn.Module):
         fmt = self.weight_format
         if fmt is not None:
             return getattr(ops, fmt.linear)(
-                x, pick(self.qweight), pick(self.weight_scale), bias
+                x, pick(self.qweight), pick(self.weight_scale), bias,
+                tile=(self.quant_gemm == "tile"),
             )
         return ops.linear(x, pick(self.weight), bias)
 

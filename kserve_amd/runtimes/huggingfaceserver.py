@@ -73,6 +73,10 @@ def engine_model_config(args):
     moe_router = getattr(args, "moe_router", None)
     if moe_router is not None:
         model_cfg.moe_router = moe_router
+    # --quant-gemm dequant|tile: quantized projections above 128 tokens
+    quant_gemm = getattr(args, "quant_gemm", None)
+    if quant_gemm is not None:
+        model_cfg.quant_gemm = quant_gemm
     return model_cfg
 
 
@@ -206,6 +210,11 @@ def build_parser():
     # KS_MOE_ROUTER, else torch)
     parser.add_argument("--moe-router", dest="moe_router", default=None,
                         choices=["torch", "fused"])
+    # quantized projections above the skinny GEMM's batch range: dequant +
+    # hipBLASLt, or the fused-dequant tile GEMM (default: KS_QUANT_GEMM, else
+    # dequant)
+    parser.add_argument("--quant-gemm", dest="quant_gemm", default=None,
+                        choices=["dequant", "tile"])
     # LoRA adapter serving (reference: --enable-lora --lora-modules name=path)
     parser.add_argument("--speculative-draft-model",
                         dest="speculative_draft_model", default=None,

@@ -5,6 +5,7 @@ shape, to judge hipBLASLt (tuned/untuned) against the HBM roofline.
 Run on GPU: python tools/gemm_bench.py [--tune]
             python tools/gemm_bench.py --w8 [--out FILE.md]
             python tools/gemm_bench.py --w4 [--out FILE.md]
+            python tools/gemm_bench.py --wq-tile [--out FILE.md]
             python tools/gemm_bench.py --moe [--out FILE.md]
             python tools/gemm_bench.py --moe-prefill [--out FILE.md]
 
@@ -17,6 +18,12 @@ threshold.
 --w4 is the same A/B behind ops.W4_MAX_TOKENS (profiles/w4_gemm.md), with
 the columns (a) ops.linear on bf16 weights, (b) the fp8-weight skinny GEMM,
 (c) the MXFP4-weight skinny GEMM and (d) MXFP4 dequant + hipBLASLt.
+
+--wq-tile is the A/B behind ops.WQ_TILE_MAX_TOKENS (profiles/
+wq_tile_gemm.md), same method, for both formats at N = 129..4096: (a)
+ops.linear on bf16 weights, (c) dequant + hipBLASLt and (d) the fused-dequant
+tile GEMM, in its remapped and its plain grid order, then forced K splits on
+the shapes the (M, K) policy splits.
 
 --moe is the A/B behind MixtralMoE.ROUTED_MAX_TOKENS (profiles/
 moe_routed.md): one Mixtral-8x7B MoE layer per token batch, the routed
@@ -42,6 +49,9 @@ parser.add_argument("--w8", action="store_true",
                     help="fp8-weight A/B table instead of the bf16 table")
 parser.add_argument("--w4", action="store_true",
                     help="MXFP4-weight A/B table instead of the bf16 table")
+parser.add_argument("--wq-tile", action="store_true",
+                    help="fused-dequant tile GEMM A/B table, fp8 and MXFP4 "
+                         "(profiles/wq_tile_gemm.md)")
 parser.add_argument("--moe", action="store_true",
                     help="routed MoE MLP against the dense-bmm path, one "
                          "Mixtral-8x7B layer (profiles/moe_routed.md)")
@@ -308,6 +318,131 @@ def bench_w4():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n" + tail + "\n")
+
+
+def bench_wq_tile():
+    """bench_w8's method (interleaved rounds, a weight set larger than the
+    Infinity Cache) above the skinny GEMMs' range. (d) is the tile GEMM with
+    the policy's split in the remapped grid order, (d plain) the same in the
+    plain order. The second table forces the split count where the policy
+    splits."""
+    import statistics
+
+    from kserve_amd import ops
+    from kserve_amd.ops.quant import quantize_fp8_per_channel, quantize_mxfp4
+
+    shapes = [  # (name, K in, M out): Llama-3-8B projections
+        ("qkv", 4096, 6144),
+        ("o", 4096, 4096),
+        ("gate_up", 4096, 28672),
+        ("down", 14336, 4096),
+    ]
+    batches = [129, 256, 512, 1024, 1536, 2048, 4096]
+    split_batches = [256, 1536]
+    rounds = 5
+    formats = {
+        "fp8": (quantize_fp8_per_channel, ops.linear_w8,
+                kserve_amd_C.wq_tile_gemm_w8),
+        "mxfp4": (quantize_mxfp4, ops.linear_w4, kserve_amd_C.wq_tile_gemm_w4),
+    }
+    for _, K, M in shapes:
+        ops.reserve_w8_scratch(dev, M, K)
+
+    def timed(fn, copies, iters):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for i in range(iters):
+            fn(i % copies)
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / iters * 1000
+
+    def medians(fns, copies, iters):
+        res = {k: [] for k in fns}
+        for r in range(rounds + 1):  # round 0 is warm-up
+            for key, fn in fns.items():
+                t = timed(fn, copies, iters)
+                if r:
+                    res[key].append(t)
+        spread = max(
+            (max(v) - min(v)) / statistics.median(v) for v in res.values()
+        )
+        return {k: statistics.median(v) for k, v in res.items()}, spread
+
+    out_lines = []
+
+    def emit(line, note=""):
+        print(line + note, flush=True)
+        out_lines.append(line)
+
+    for fmt, (quantize, linear_wq, tile) in formats.items():
+        emit(f"\n## {fmt}\n")
+        emit("| shape | K | M | S | N | (a) bf16 us | (c) dequant+GEMM us "
+             "| (d) tile us | (d plain) us | (c)/(a) | (d)/(a) | (d)<=(c) |")
+        emit("|---|---|---|---|---|---|---|---|---|---|---|---|")
+        wins = {n: True for n in batches}
+        sweep = []
+        for name, K, M in shapes:
+            copies = max(2, -(-(768 << 20) // (M * K)))
+            gen = torch.Generator(device=dev).manual_seed(0)
+            ws, qs, ss = [], [], []
+            for _ in range(copies):
+                w = torch.randn(M, K, dtype=torch.bfloat16, device=dev,
+                                generator=gen) * 0.02
+                q, sc = quantize(w)
+                ws.append(w); qs.append(q); ss.append(sc)
+            S = kserve_amd_C.wq_tile_nsplit(M, K)
+            for N in batches:
+                x = torch.randn(N, K, dtype=torch.bfloat16, device=dev,
+                                generator=gen) / 8
+                out = torch.empty(N, M, dtype=torch.bfloat16, device=dev)
+                iters = max(min(args.iters, 20), 2 * copies)
+                fns = {
+                    "a": lambda i: ops.linear(x, ws[i]),
+                    "c": lambda i: linear_wq(x, qs[i], ss[i]),
+                    "d": lambda i: tile(out, x, qs[i], ss[i], None, 0, False),
+                    "p": lambda i: tile(out, x, qs[i], ss[i], None, 0, True),
+                }
+                t, spread = medians(fns, copies, iters)
+                # (d), the order ops dispatches, decides; (d plain) is
+                # recorded beside it
+                wins[N] = wins[N] and t["d"] <= t["c"]
+                emit(f"| {name} | {K} | {M} | {S} | {N} | {t['a']:.1f} | "
+                     f"{t['c']:.1f} | {t['d']:.1f} | {t['p']:.1f} | "
+                     f"{t['c'] / t['a']:.2f} | {t['d'] / t['a']:.2f} | "
+                     f"{'yes' if t['d'] <= t['c'] else 'no'} |",
+                     f"  spread {spread:.0%}")
+                if S > 1 and N in split_batches:
+                    forced = {
+                        s_: (lambda i, s_=s_: tile(out, x, qs[i], ss[i], None,
+                                                   s_, False))
+                        for s_ in (1, 2, 4, 8)
+                    }
+                    ts, _ = medians(forced, copies, iters)
+                    sweep.append(
+                        f"| {name} | {K} | {M} | {N} | "
+                        + " | ".join(f"{ts[s_]:.1f}" for s_ in (1, 2, 4, 8))
+                        + " |"
+                    )
+            del ws, qs, ss
+            torch.cuda.empty_cache()
+        emit("\nForced K splits (us), remapped order:\n")
+        emit("| shape | K | M | N | S=1 | S=2 | S=4 | S=8 |")
+        emit("|---|---|---|---|---|---|---|---|")
+        for line in sweep:
+            emit(line)
+        # largest measured N up to which (d) <= (c) on all four shapes
+        chosen = 0
+        for n in batches:
+            if not wins[n]:
+                break
+            chosen = n
+        emit(f"\nWQ_TILE_MAX_TOKENS[{fmt!r}] by this table: {chosen}")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(out_lines) + "\n")
 
 
 def bench_moe():
@@ -661,6 +796,9 @@ if args.moe:
         bench_moe_quant(args.quantization)
     else:
         bench_moe()
+    sys.exit(0)
+if args.wq_tile:
+    bench_wq_tile()
     sys.exit(0)
 if args.w8:
     bench_w8()
