@@ -25,6 +25,7 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 # new kernels go here.
 NO_PACKED_FP32 = {
     "moe.hip", "moe_prefill.hip", "moe_router.hip", "wq_tile_gemm.hip",
+    "attention_ctx_packed.hip",
 }
 NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
@@ -37,6 +38,7 @@ KERNEL_SOURCES = [
     "kv_transfer.hip",
     "attention_decode.hip",
     "attention_prefill.hip",
+    "attention_ctx_packed.hip",
     "sampling.hip",
     "logit_process.hip",
     "skinny_gemm.hip",

@@ -84,8 +84,22 @@ class ModelConfig:
     quant_gemm: str = field(
         default_factory=lambda: os.environ.get("KS_QUANT_GEMM") or "dequant"
     )
+    # which kernel attends a short run of new tokens to the paged context
+    # (speculative verification, prefix-cache hits, chunk tails): "tiled"
+    # (the chunked-prefill kernel, any length) or "packed" (the GQA-packed
+    # split-KV kernel, ops.context_attention_varlen with kernel="packed";
+    # steps outside ops.context_packed_supported run "tiled"). The
+    # environment variable KS_CTX_ATTN sets the default.
+    ctx_attn: str = field(
+        default_factory=lambda: os.environ.get("KS_CTX_ATTN") or "tiled"
+    )
 
     def __post_init__(self):
+        if self.ctx_attn not in ("tiled", "packed"):
+            raise ValueError(
+                f"unknown ctx_attn {self.ctx_attn!r}; "
+                "supported: 'tiled', 'packed'"
+            )
         if self.quant_gemm not in ("dequant", "tile"):
             raise ValueError(
                 f"unknown quant_gemm {self.quant_gemm!r}; "

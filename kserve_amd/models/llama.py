@@ -60,6 +60,8 @@ class LlamaAttention(nn.Module):
         # Mistral-style sliding window (0/None = full attention); applied
         # in-kernel as a lower bound on attended positions
         self.sliding_window = int(getattr(config, "sliding_window", 0) or 0)
+        # ModelConfig.ctx_attn: short runs against the paged context
+        self.ctx_attn = getattr(config, "ctx_attn", "tiled")
         self.qkv_proj = QKVParallelLinear(
             config.hidden_size,
             config.head_dim,
@@ -105,10 +107,17 @@ class LlamaAttention(nn.Module):
             if meta.context_lens is not None:
                 # chunked prefill: attend to the whole paged context (past
                 # chunks' KV + this chunk's, written to pages above)
+                packed = self.ctx_attn == "packed" and (
+                    ops.context_packed_supported(
+                        meta.max_seqlen, self.num_heads_local,
+                        self.num_kv_heads_local, self.head_dim,
+                    )
+                )
                 out = ops.context_attention_varlen(
                     q, k_cache, v_cache, meta.block_tables, meta.cu_seqlens,
                     meta.context_lens, meta.max_seqlen, self.scale,
                     window=self.sliding_window,
+                    kernel="packed" if packed else "tiled",
                 )
             else:
                 out = ops.flash_prefill_varlen(

@@ -145,6 +145,34 @@ def flash_prefill_varlen(
     )
 
 
+# packed context attention (attention_ctx_packed.hip): MFMA rows one workgroup
+# holds, = max_q_len * (Hq / Hkv)
+CTX_PACKED_MAX_ROWS = 64
+# split rule constants, measured (profiles/ctx_packed_attn.md): workgroups the
+# grid aims at, the fewest 32-token page pairs a split keeps, the most splits
+CTX_PACKED_TARGET_WGS = 256
+CTX_PACKED_MIN_PAIRS = 8
+CTX_PACKED_MAX_SPLITS = 16
+
+
+def context_packed_supported(max_q_len: int, Hq: int, Hkv: int, D: int) -> bool:
+    """Whether context_attention_varlen(kernel="packed") takes this shape."""
+    if D not in (64, 128) or Hkv <= 0 or Hq % Hkv != 0 or max_q_len < 0:
+        return False
+    return max_q_len * (Hq // Hkv) <= CTX_PACKED_MAX_ROWS
+
+
+def ctx_packed_splits(S: int, Hkv: int, max_pairs: int) -> int:
+    """Context splits of the packed kernel: enough workgroups to fill the
+    chip, while a split keeps at least CTX_PACKED_MIN_PAIRS page pairs (two
+    per wave). A function of the batch shape and the table width only, so a
+    shape always runs at the same split count."""
+    base = max(1, S * Hkv)
+    n = -(-CTX_PACKED_TARGET_WGS // base)
+    n = min(n, max_pairs // CTX_PACKED_MIN_PAIRS, CTX_PACKED_MAX_SPLITS)
+    return max(1, n)
+
+
 def context_attention_varlen(
     q: torch.Tensor,
     k_cache: torch.Tensor,
@@ -155,17 +183,64 @@ def context_attention_varlen(
     max_q_len: int,
     scale: float,
     window: int = 0,
+    kernel: str = "tiled",
+    splits: int = 0,
 ) -> torch.Tensor:
     """Prefill attention against the paged cache (chunked prefill): the
     chunk's KV must already be written to the cache; queries attend causally
     to the whole per-seq context (bounded below by the sliding window when
     window > 0).
 
+    kernel: "tiled" (one workgroup per query head and 128 rows, any q length)
+    or "packed" (all heads of a KV head times all new tokens packed into one
+    MFMA row block, context split over workgroups; for short runs, see
+    context_packed_supported; ValueError outside its range). splits, packed
+    only: 0 lets ctx_packed_splits choose, a positive value forces that many
+    context splits (clamped to the table's page pairs). The CPU reference
+    ignores both.
+
     Cache contract, as for paged_attention_decode: exact for any finite
     stale data in slots at or past context_lens and in pages behind unused
     block-table entries (which must be valid ids), undefined for non-finite
     data there; the cache must never hold non-finite values the model did
     not write."""
+    if kernel not in ("tiled", "packed"):
+        raise ValueError(
+            f"unknown context attention kernel {kernel!r}; "
+            "supported: 'tiled', 'packed'"
+        )
+    if q.is_cuda and kernel == "packed":
+        Hq, D = q.shape[1], q.shape[2]
+        Hkv = k_cache.shape[1]
+        if not context_packed_supported(int(max_q_len), Hq, Hkv, D):
+            raise ValueError(
+                f"packed context attention takes max_q_len * (Hq / Hkv) <= "
+                f"{CTX_PACKED_MAX_ROWS} and head_dim 64 or 128; got "
+                f"max_q_len={max_q_len}, Hq={Hq}, Hkv={Hkv}, D={D}"
+            )
+        S = cu_seqlens_q.shape[0] - 1
+        max_pairs = max(1, (block_tables.shape[1] + 1) // 2)
+        if window > 0:
+            max_pairs = min(max_pairs, (window + int(max_q_len)) // 32 + 2)
+        if splits > 0:
+            n_splits = min(int(splits), max_pairs)
+        else:
+            n_splits = ctx_packed_splits(S, Hkv, max_pairs)
+        out = torch.empty_like(q)
+        rows = int(max_q_len) * (Hq // Hkv)
+        rows_pad = 16 if rows <= 16 else (32 if rows <= 32 else 64)
+        ws_o = ws_ml = None   # fp32 split partials, one split needs none
+        if n_splits > 1:
+            n_part = S * Hkv * n_splits * rows_pad
+            ws = torch.empty(n_part * (D + 2), dtype=torch.float32,
+                             device=q.device)
+            ws_o, ws_ml = ws[:n_part * D], ws[n_part * D:]
+        _native("context_packed").context_packed_varlen(
+            out, q, k_cache, v_cache, block_tables, context_lens,
+            cu_seqlens_q, ws_o, ws_ml, int(max_q_len), scale, int(window),
+            n_splits,
+        )
+        return out
     if q.is_cuda:
         out = torch.empty_like(q)
         _native("context_prefill").context_prefill_varlen(

@@ -32,6 +32,11 @@ hipError_t ks_context_prefill_varlen(void*, const void*, const void*,
                                      const void*, int, int, int, int, int,
                                      int, float, long, int, int,
                                      hipStream_t);
+hipError_t ks_context_packed_varlen(void*, const void*, const void*,
+                                    const void*, const void*, const void*,
+                                    const void*, void*, void*, int, int, int,
+                                    int, int, int, float, long, int, int, int,
+                                    hipStream_t);
 hipError_t ks_paged_attention_decode_fp8(void*, const void*, const void*,
                                          const void*, const void*,
                                          const void*, float, int, int, int,
@@ -387,6 +392,65 @@ void context_prefill_varlen(at::Tensor& out, at::Tensor& q,
                 (float)scale, (long)q.stride(0), fp8, (int)window,
                 current_stream()),
             "context_prefill_varlen");
+}
+
+// GQA-packed split-KV variant for max_q_len * (Hq / Hkv) <= 64. ws_o / ws_ml
+// are the fp32 split workspaces ([S, Hkv, n_splits, rows_pad, D] and
+// [..., 2], rows_pad = 16, 32 or 64); required only when n_splits > 1.
+void context_packed_varlen(at::Tensor& out, at::Tensor& q,
+                           at::Tensor& k_cache, at::Tensor& v_cache,
+                           at::Tensor& block_tables, at::Tensor& ctx_lens,
+                           at::Tensor& cu_seqlens_q,
+                           c10::optional<at::Tensor> ws_o,
+                           c10::optional<at::Tensor> ws_ml,
+                           int64_t max_q_len, double scale,
+                           int64_t window, int64_t n_splits) {
+  CHECK_BF16_CONTIG(out);
+  CHECK_BF16_ROWS(q);
+  CHECK_KV_CACHE(k_cache);
+  CHECK_KV_CACHE(v_cache);
+  TORCH_CHECK(block_tables.scalar_type() == at::kInt, "block_tables int32");
+  TORCH_CHECK(block_tables.is_contiguous(), "block_tables contiguous");
+  TORCH_CHECK(ctx_lens.scalar_type() == at::kInt, "ctx_lens int32");
+  TORCH_CHECK(cu_seqlens_q.scalar_type() == at::kInt, "cu_seqlens_q int32");
+  TORCH_CHECK(k_cache.size(2) == 16, "block_size must be 16");
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(),
+              "k_cache and v_cache differ in dtype");
+  int num_seqs = cu_seqlens_q.size(0) - 1;
+  int Hq = q.size(1);
+  int Hkv = k_cache.size(1);
+  int D = q.size(2);
+  TORCH_CHECK(k_cache.size(3) == D, "cache head_dim differs from q");
+  TORCH_CHECK(block_tables.size(0) >= num_seqs && ctx_lens.size(0) >= num_seqs,
+              "block_tables / ctx_lens shorter than the batch");
+  TORCH_CHECK(n_splits >= 1, "n_splits >= 1");
+  void* ws_o_ptr = nullptr;
+  void* ws_ml_ptr = nullptr;
+  if (n_splits > 1) {
+    TORCH_CHECK(ws_o.has_value() && ws_ml.has_value(),
+                "n_splits > 1 needs the ws_o and ws_ml workspaces");
+    const int64_t rows = max_q_len * (Hq / Hkv);
+    const int64_t rows_pad = rows <= 16 ? 16 : (rows <= 32 ? 32 : 64);
+    const int64_t need = (int64_t)num_seqs * Hkv * n_splits * rows_pad;
+    TORCH_CHECK(ws_o->is_cuda() && ws_o->scalar_type() == at::kFloat &&
+                    ws_o->is_contiguous() && ws_o->numel() >= need * D,
+                "ws_o: contiguous fp32, S*Hkv*n_splits*rows_pad*D");
+    TORCH_CHECK(ws_ml->is_cuda() && ws_ml->scalar_type() == at::kFloat &&
+                    ws_ml->is_contiguous() && ws_ml->numel() >= need * 2,
+                "ws_ml: contiguous fp32, S*Hkv*n_splits*rows_pad*2");
+    ws_o_ptr = ws_o->data_ptr();
+    ws_ml_ptr = ws_ml->data_ptr();
+  }
+  int fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn ? 1 : 0;
+  check_hip(ks_context_packed_varlen(
+                out.data_ptr(), q.data_ptr(), k_cache.data_ptr(),
+                v_cache.data_ptr(), block_tables.data_ptr(),
+                ctx_lens.data_ptr(), cu_seqlens_q.data_ptr(),
+                ws_o_ptr, ws_ml_ptr, num_seqs, (int)max_q_len,
+                Hq, Hkv, D, (int)block_tables.size(1), (float)scale,
+                (long)q.stride(0), fp8, (int)window, (int)n_splits,
+                current_stream()),
+            "context_packed_varlen");
 }
 
 void layer_norm(at::Tensor& out, at::Tensor& input, at::Tensor& weight,
@@ -1267,6 +1331,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("causal") = true, pybind11::arg("window") = 0);
   m.def("context_prefill_varlen", &context_prefill_varlen,
         "MFMA prefill attention against the paged KV cache (chunked prefill)");
+  m.def("context_packed_varlen", &context_packed_varlen,
+        "paged-context attention for short query runs (GQA-packed, split-KV)");
   m.def("layer_norm", &layer_norm, "LayerNorm (bf16)");
   m.def("fused_add_layer_norm", &fused_add_layer_norm,
         "residual-add + LayerNorm");

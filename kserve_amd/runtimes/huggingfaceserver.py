@@ -77,6 +77,10 @@ def engine_model_config(args):
     quant_gemm = getattr(args, "quant_gemm", None)
     if quant_gemm is not None:
         model_cfg.quant_gemm = quant_gemm
+    # --ctx-attn tiled|packed: short query runs against the paged context
+    ctx_attn = getattr(args, "ctx_attn", None)
+    if ctx_attn is not None:
+        model_cfg.ctx_attn = ctx_attn
     return model_cfg
 
 
@@ -215,6 +219,11 @@ def build_parser():
     # dequant)
     parser.add_argument("--quant-gemm", dest="quant_gemm", default=None,
                         choices=["dequant", "tile"])
+    # short runs of new tokens against the paged context (speculative
+    # verification, prefix-cache hits): the chunked-prefill kernel, or the
+    # GQA-packed split-KV kernel (default: KS_CTX_ATTN, else tiled)
+    parser.add_argument("--ctx-attn", dest="ctx_attn", default=None,
+                        choices=["tiled", "packed"])
     # LoRA adapter serving (reference: --enable-lora --lora-modules name=path)
     parser.add_argument("--speculative-draft-model",
                         dest="speculative_draft_model", default=None,
